@@ -19,10 +19,19 @@ bench.py starts torch.distributed.run as a CHILD process (never an exec) before 
 the GPU, and exits with its return code; rank 0's JSON line is the child's stdout. A WORLD_SIZE
 that disagrees with --gpus is refused (exit 2).
 
-Extra fields: roofline (dominant kernel, algorithmic bytes / HIP-event kernel time vs the
-8 TB/s HBM3E spec peak), cpu_baseline (the C oracle, a scalar port of the Go path, timed on
-this host's cores on a bounded sample), secondary (1500 B, IMIX, 9000 B jumbo, and the
-cache-resident variant of the headline; N=1 only).
+A plain run does what the headline figure needs and no more: set up, warm up, time --steps steps,
+write the outputs if --dump-outputs is given, print the result line (with the roofline of the
+headline kernel against the 8 TB/s HBM3E spec peak, which costs no run of its own).
+
+--full adds everything else: the measured read peak and the size-matched probes beside the
+roofline, every rank's validation of its shard (exit 3 if it fails), whole_shard_launch (N > 1),
+cpu_baseline (the C oracle, a scalar port of the Go path, timed on this host's cores), secondary
+(1500 B, IMIX, 9000 B jumbo, the cache-resident variant of the headline, ...; N=1 only) and the
+detail file. --no-cpu and --no-secondary trim a --full run. The secondaries run --steps steps up to
+SECONDARY_MAX_STEPS (1000, the default); the headline always times exactly --steps.
+
+--dump-outputs DIR writes what the last timed step computed, the record array a caller of
+halo_rx_parse_batch_device receives, as float32 .npy files (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -39,6 +48,10 @@ sys.path.insert(0, ROOT)
 METRIC = "Mpps + Gbit/s device-resident parse+cksum, 64B & 1500B frames, 1/2/4/8 GPU"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 RESULT_BYTES = 32
+DETAIL_DIR = "bench_out"  # under the repository root: where --full leaves bench_detail.json
+DUMP_ROWS = 1 << 18  # --dump-outputs keeps at most this many records: 256k x 32 B as float32 = 32 MiB
+DUMP_SEED = 0x44554D50
+SECONDARY_MAX_STEPS = 1000  # --full: steps and warm-up launches of a secondary are capped here
 
 
 def log(*a):
@@ -53,11 +66,17 @@ def parse_args():
     p.add_argument("--frames", type=int, default=1 << 20, help="frames per batch per GPU")
     p.add_argument("--rotate", type=int, default=16,
                    help="distinct batches cycled through (frames x rotate = one GPU's shard: 16M = config 4 / 8)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beyond the headline: measured read peak and size-matched "
+                        "probes, shard validation, secondaries, CPU baselines, the detail file")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's records to DIR/*.npy (float32)")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
-    p.add_argument("--no-cpu", action="store_true")
-    p.add_argument("--no-secondary", action="store_true")
-    p.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                   help="the full record (prose, probe tables, curves); stdout carries the compact line")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondaries")
+    p.add_argument("--detail", default=None,
+                   help="the full record (prose, probe tables, curves); stdout carries the compact line. "
+                        f"Default with --full: {os.path.join(DETAIL_DIR, 'bench_detail.json')}; without: not written")
     return p.parse_args()
 
 
@@ -1553,13 +1572,37 @@ def compact_line(line: dict, limit: int = LINE_LIMIT) -> dict:
     return out
 
 
-def emit_line(line: dict, detail_path: str) -> str:
-    """Write the full record to `detail_path` (a JSON file) and print the compact line on stdout."""
+def dump_outputs(out, path: str) -> dict:
+    """--dump-outputs: what the last timed step left in its record array (`out`, n x 32 B on the
+    device), as float32 arrays a later build's run with the same arguments can be compared with.
+    records.npy is [rows, 32], one float per record byte (exact); record_rows.npy the frame index
+    of each row within the step's batch. Up to DUMP_ROWS records are kept: all of them, or a sorted
+    sample drawn once from DUMP_SEED (the same rows in every run with the same --frames)."""
+    import numpy as np
+    import torch
+
+    n = out.shape[0]
+    if n > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_ROWS, replace=False))
+    else:
+        rows = np.arange(n)
+    rec = out[torch.from_numpy(rows).to(out.device)].cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "records.npy"), rec.astype(np.float32))
+    np.save(os.path.join(path, "record_rows.npy"), rows.astype(np.float64))
+    log(f"[bench] outputs: {rows.size} of {n} records of the last timed step in {path}")
+    return {"dir": path, "records": int(rows.size), "of": int(n)}
+
+
+def emit_line(line: dict, detail_path) -> str:
+    """Write the full record to `detail_path` (a JSON file; None: not written) and print the compact
+    line on stdout."""
     try:
-        os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
-        with open(detail_path, "w") as f:
-            json.dump(line, f, indent=1)
-        log(f"[bench] full record: {detail_path}")
+        if detail_path:
+            os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
+            with open(detail_path, "w") as f:
+                json.dump(line, f, indent=1)
+            log(f"[bench] full record: {detail_path}")
     except OSError as e:
         log(f"[bench] could not write {detail_path}: {e}")
     s = json.dumps(compact_line(line))
@@ -1590,7 +1633,10 @@ def main():
 
     _lib.check("halo_rx_init", _lib.lib.halo_rx_init(gpu))
     netif = NetIf.make()  # eth0 of example.UsePcapDev (example/example.go:768-773)
-    measure_read_peak(dev, d)
+    if args.detail is None and args.full:
+        args.detail = os.path.join(ROOT, DETAIL_DIR, "bench_detail.json")
+    if args.full:
+        measure_read_peak(dev, d)
     n = args.frames
     shard_frames = n * args.rotate
 
@@ -1602,6 +1648,9 @@ def main():
     out = torch.empty((n, RESULT_BYTES), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
     wall, kern_ms = time_steps(batches, out, netif, flags=1, hint=64, steps=args.steps, warmup=args.warmup, d=d)
+    dumped = None
+    if args.dump_outputs and d.rank == 0:  # before anything else reuses the record array
+        dumped = dump_outputs(out, args.dump_outputs)
     per_rank_kms = d.gather(kern_ms)
     frames_total = n * args.steps * d.world
     mpps = frames_total / wall / 1e6
@@ -1614,7 +1663,8 @@ def main():
     ident = device_identity(gpu)
     ident["rank"] = d.rank
     ident["kernel_ms"] = round(kern_ms, 5)
-    ident["validation"] = validate_shard(batches, netif, dev, d.rank)
+    if args.full:
+        ident["validation"] = validate_shard(batches, netif, dev, d.rank)
     ranks = d.gather_obj(ident)
     distinct = len({r["pci_bus_id"] for r in ranks}) == d.world
     if d.world == 1:
@@ -1641,28 +1691,37 @@ def main():
         "alg_bytes_per_launch": alg,
         "per_rank": ranks,
         "distinct_devices": distinct,
-        "validated": all(r["validation"]["valid"] for r in ranks),
+        "full": args.full,
         "cpu_baseline": None,
     }
+    if args.full:
+        line["validated"] = all(r["validation"]["valid"] for r in ranks)
+    if dumped:
+        line["dumped_outputs"] = dumped
     if d.world > 1:
-        # the same shards, each parsed whole in ONE launch per step (16M frames per GPU per launch)
-        sh_out = torch.empty((shard_frames, RESULT_BYTES), dtype=torch.uint8, device=dev)
-        st = max(5, args.steps // 5)
-        w2, k2 = time_steps([shard], sh_out, netif, flags=1, hint=64, steps=st, warmup=2, d=d)
-        ks = d.gather(k2)
-        line["whole_shard_launch"] = {
-            "value": round(shard_frames * d.world * st / w2 / 1e6, 2), "unit": "Mpps", "steps": st,
-            "ms_per_step": round(w2 / st * 1e3, 4), "per_rank_kernel_ms": [round(k, 5) for k in ks],
-            "what": f"each GPU's {shard_frames >> 20}M-frame shard in one launch per step"}
-        del sh_out
+        if args.full:
+            # the same shards, each parsed whole in ONE launch per step (16M frames per GPU per launch)
+            sh_out = torch.empty((shard_frames, RESULT_BYTES), dtype=torch.uint8, device=dev)
+            st = max(5, args.steps // 5)
+            w2, k2 = time_steps([shard], sh_out, netif, flags=1, hint=64, steps=st, warmup=2, d=d)
+            ks = d.gather(k2)
+            line["whole_shard_launch"] = {
+                "value": round(shard_frames * d.world * st / w2 / 1e6, 2), "unit": "Mpps", "steps": st,
+                "ms_per_step": round(w2 / st * 1e3, 4), "per_rank_kernel_ms": [round(k, 5) for k in ks],
+                "what": f"each GPU's {shard_frames >> 20}M-frame shard in one launch per step"}
+            del sh_out
         if not distinct:
             line["note"] = ("ranks shared a device (fewer GPUs than ranks): a rehearsal of the N-rank path, "
                             "not a scaling point")
         d.close()
         if d.rank == 0:
             emit_line(line, args.detail)
-        sys.exit(0 if line["validated"] else 3)
+        sys.exit(0 if line.get("validated", True) else 3)
     del shard
+    if not args.full:  # a plain run ends here: the headline and what it needed
+        d.close()
+        emit_line(line, args.detail)
+        return
     line["roofline"]["note"] = ("achieved = (frame bytes + 6 B metadata + 32 B record) per launch / average "
                                 "launch duration (one HIP event pair over the timed region / steps); "
                                 "peak = HBM3E spec; traffic = HBM request bytes per launch from profiles/pmc_summary.json "
@@ -1678,32 +1737,40 @@ def main():
 
     if d.world == 1 and not args.no_secondary:
         sec = {}
+        # The secondaries run at most SECONDARY_MAX_STEPS steps (the default --steps) however many the
+        # headline times: their per-launch figures gain nothing beyond that, the host-memory rows cost
+        # milliseconds per step, and the status histograms are 32-bit counters of frames x launches.
+        sec_steps = min(args.steps, SECONDARY_MAX_STEPS)
+        sec_warmup = min(args.warmup, SECONDARY_MAX_STEPS)
+        line["secondary_steps"] = sec_steps
         # cache-resident variant of the headline (one batch, 102 MB < 256 MB Infinity Cache)
-        w1, k1 = time_steps(batches[:1], out, netif, flags=1, hint=64, steps=args.steps, warmup=args.warmup, d=d)
-        sec["config2_mall_resident"] = {"mpps": round(n * args.steps / w1 / 1e6, 1), "kernel_ms": round(k1, 5),
+        w1, k1 = time_steps(batches[:1], out, netif, flags=1, hint=64, steps=sec_steps, warmup=sec_warmup, d=d)
+        sec["config2_mall_resident"] = {"mpps": round(n * sec_steps / w1 / 1e6, 1), "kernel_ms": round(k1, 5),
                                         "roofline": roofline(alg, k1)}
         # the same headline workload writing the compact 16 B record (verdict + 5-tuple only)
         from halo_amd._lib import HALO_RX_RECORD_COMPACT
 
-        wc, kc = time_steps(batches, out, netif, flags=1 | HALO_RX_RECORD_COMPACT, hint=64, steps=args.steps,
-                            warmup=args.warmup, d=d)
+        wc, kc = time_steps(batches, out, netif, flags=1 | HALO_RX_RECORD_COMPACT, hint=64, steps=sec_steps,
+                            warmup=sec_warmup, d=d)
         algc = fbytes + n * (4 + 2 + 16)
-        sec["config2_compact_record16"] = {"mpps": round(n * args.steps / wc / 1e6, 1), "kernel_ms": round(kc, 5),
+        sec["config2_compact_record16"] = {"mpps": round(n * sec_steps / wc / 1e6, 1), "kernel_ms": round(kc, 5),
                                            "roofline": roofline(algc, kc)}
         # the headline with the §5 metrics output on: every launch counts into a status histogram
         hist = torch.zeros(14, dtype=torch.int32, device=dev)
-        wh, kh = time_steps(batches, out, netif, flags=1, hint=64, steps=args.steps, warmup=args.warmup, d=d,
+        wh, kh = time_steps(batches, out, netif, flags=1, hint=64, steps=sec_steps, warmup=sec_warmup, d=d,
                             hist=hist)
-        hsum = int(hist.sum().item())
+        hv = hist.cpu().numpy().view(np.uint32).astype(np.int64)  # the counters are uint32_t
+        hsum = int(hv.sum())
         sec["config2_status_histogram"] = {
-            "mpps": round(n * args.steps / wh / 1e6, 1), "kernel_ms": round(kh, 5), "roofline": roofline(alg, kh),
-            "vs_headline": round(kern_ms / kh, 4), "hist_frames": hsum, "hist_ok": int(hist[0].item()),
+            "mpps": round(n * sec_steps / wh / 1e6, 1), "kernel_ms": round(kh, 5), "roofline": roofline(alg, kh),
+            "vs_headline": round(kern_ms / kh, 4), "hist_frames": hsum, "hist_ok": int(hv[0]),
             "what": "the headline step with d_status_hist (block-aggregated in LDS, then fence-free self-completing (arrivals, count) words: one level of 16-block runs for grids up to 16384 blocks, a two-level tree above; the lane grid halved up to 1M frames)"}
-        assert hsum == n * (args.steps + args.warmup) and int(hist[0].item()) == hsum
+        assert n * (sec_steps + sec_warmup) < 1 << 32, "status histogram: 32-bit counters would wrap"
+        assert hsum == n * (sec_steps + sec_warmup) and int(hv[0]) == hsum, (hsum, n, sec_steps, sec_warmup)
         # the batch stream handed over 8 batches per launch (halo_rx_parse_batches_device): the ramp
         # and tail of a 1M-frame launch paid once per 8M frames
-        sec["config2_batch_stream"] = batch_stream_secondary(batches, netif, args.steps, args.warmup, d, kern_ms)
-        sec["config2_queues"] = queues_secondary(batches, netif, args.steps, args.warmup, d, kern_ms)
+        sec["config2_batch_stream"] = batch_stream_secondary(batches, netif, sec_steps, sec_warmup, d, kern_ms)
+        sec["config2_queues"] = queues_secondary(batches, netif, sec_steps, sec_warmup, d, kern_ms)
 
         # forward / transmit rewrite (§8f row f2) on the headline frames: DNAT + SNAT + DPDK fill
         import numpy as np
@@ -1711,10 +1778,10 @@ def main():
         ops_h = tx_ops_for(n)
         ops_d = torch.from_numpy(ops_h.view(np.uint8)).to(dev)
         res_d = torch.empty(n, dtype=torch.uint8, device=dev)
-        wt, kt = time_tx_steps(batches, ops_d, res_d, flags=1, hint=64, steps=args.steps, warmup=args.warmup, d=d)
+        wt, kt = time_tx_steps(batches, ops_d, res_d, flags=1, hint=64, steps=sec_steps, warmup=sec_warmup, d=d)
         algt = fbytes + n * (4 + 2 + 16 + 1 + TX_WRITE_BYTES)
         sec["tx_fixup_config2_nat_dpdk"] = {
-            "mpps": round(n * args.steps / wt / 1e6, 1), "kernel_ms": round(kt, 5),
+            "mpps": round(n * sec_steps / wt / 1e6, 1), "kernel_ms": round(kt, 5),
             "roofline": roofline(algt, kt, load_traffic("tx_config2")), "alg_bytes_per_launch": algt,
             "steps": "NatChangeDst + NatChangeSrc + eth_tx DPDK fill, per-frame addresses/ports"}
         # the probe moves what the memory system must: the frames + metadata + ops in, and one
@@ -1731,29 +1798,29 @@ def main():
                 lambda: O.tx_batch(host, lay0["offsets_dw"][:m], lay0["lens"][:m], ops_h[:m], flags=1), m, 2.0, "Mpps",
                 f"{m} x 64B frames of batch 0, same ops (oracle/halo_tx_oracle.c)")
         del ops_d, res_d
-        sec["flow_hash_config2_nat_wan"] = flow_hash_secondary(batches, out, netif, args.steps, args.warmup, d,
+        sec["flow_hash_config2_nat_wan"] = flow_hash_secondary(batches, out, netif, sec_steps, sec_warmup, d,
                                                                with_cpu=not args.no_cpu)
         sec["rx_flow_fused_config2_nat_wan"] = rx_flow_fused_secondary(
-            batches, out, netif, args.steps, args.warmup, d, kern_ms, sec["flow_hash_config2_nat_wan"]["kernel_ms"])
+            batches, out, netif, sec_steps, sec_warmup, d, kern_ms, sec["flow_hash_config2_nat_wan"]["kernel_ms"])
         del batches
         torch.cuda.empty_cache()
-        sec.update(tx_build_secondary(dev, args.steps, args.warmup, d, with_cpu=not args.no_cpu))
-        sec["lo_drain_1M_50B"] = lo_drain_secondary(dev, netif, args.steps, args.warmup, d, with_cpu=not args.no_cpu)
+        sec.update(tx_build_secondary(dev, sec_steps, sec_warmup, d, with_cpu=not args.no_cpu))
+        sec["lo_drain_1M_50B"] = lo_drain_secondary(dev, netif, sec_steps, sec_warmup, d, with_cpu=not args.no_cpu)
         torch.cuda.empty_cache()
-        sec["xxh3_kcp_segments_1M"] = xxh3_secondary(dev, max(5, args.steps // 10), 2, d, with_cpu=not args.no_cpu)
+        sec["xxh3_kcp_segments_1M"] = xxh3_secondary(dev, max(5, sec_steps // 10), 2, d, with_cpu=not args.no_cpu)
         torch.cuda.empty_cache()
-        sec["route_lpm_500k_prefixes"] = route_secondary(dev, max(10, args.steps // 4), 3, d, with_cpu=not args.no_cpu)
+        sec["route_lpm_500k_prefixes"] = route_secondary(dev, max(10, sec_steps // 4), 3, d, with_cpu=not args.no_cpu)
         torch.cuda.empty_cache()
-        line["config4_128M_one_gpu"] = config4_one_gpu(dev, netif, d, max(20, args.steps // 4), 3)
+        line["config4_128M_one_gpu"] = config4_one_gpu(dev, netif, d, max(20, sec_steps // 4), 3)
         # SURVEY §8d's mutation set: 1/64 of the frames with one bit flipped in [14, L)
         bm = make_batches(dev, netif, n=n, rotate=8, rank=0, mutate_shift=6)
         om = torch.empty((n, RESULT_BYTES), dtype=torch.uint8, device=dev)
         hm = torch.zeros(14, dtype=torch.int32, device=dev)
-        wm, km = time_steps(bm, om, netif, flags=1, hint=64, steps=args.steps, warmup=args.warmup, d=d, hist=hm)
+        wm, km = time_steps(bm, om, netif, flags=1, hint=64, steps=sec_steps, warmup=sec_warmup, d=d, hist=hm)
         fbm = frame_bytes(bm[0])
-        hmn = hm.cpu().numpy().astype(np.int64)
+        hmn = hm.cpu().numpy().view(np.uint32).astype(np.int64)
         sec["config2_mutated_1in64"] = {
-            "mpps": round(n * args.steps / wm / 1e6, 1), "kernel_ms": round(km, 5),
+            "mpps": round(n * sec_steps / wm / 1e6, 1), "kernel_ms": round(km, 5),
             "roofline": roofline(fbm + n * (6 + RESULT_BYTES), km, frame_bytes=fbm),
             "failing_frac": round(float(hmn[1:].sum() / hmn.sum()), 5),
             "status_hist": {STATUS_NAMES[i]: int(hmn[i]) for i in range(14) if hmn[i]},
@@ -1773,7 +1840,7 @@ def main():
             bs = make_batches(dev, netif, n=nn, rotate=rot, rank=0, **kw)
             o2 = torch.empty((nn, RESULT_BYTES), dtype=torch.uint8, device=dev)
             torch.cuda.synchronize()
-            steps = max(5, args.steps // 5)
+            steps = max(5, sec_steps // 5)
             w2, k2 = time_steps(bs, o2, netif, flags=flags, hint=hint, steps=steps, warmup=2, d=d,
                                 strided_len=strided_len)
             fb = frame_bytes(bs[0])
@@ -1798,11 +1865,11 @@ def main():
         # end to end from host memory: pinned H2D -> kernel -> D2H, double
         # buffered in 64 MB chunks by halo_rx_parse_batch_host; the frame buffer is registered
         # (pinned in place) so each chunk is one DMA straight from it
-        sec.update(e2e_host(dev, netif, steps=max(3, args.steps // 40)))
+        sec.update(e2e_host(dev, netif, steps=max(3, sec_steps // 40)))
         # the drop-in surface at small batch sizes (go/gpurx ParseBatch, single-frame Parse*)
         sec["dropin_small_batch"] = dropin_small_batch(dev, netif, with_cpu=not args.no_cpu)
         # halo's SPSC packet ring as the source (BASELINE config 1 over a Wire)
-        sec.update(ring_secondary(dev, netif, max(10, args.steps // 4), 3, d, with_cpu=not args.no_cpu))
+        sec.update(ring_secondary(dev, netif, max(10, sec_steps // 4), 3, d, with_cpu=not args.no_cpu))
         torch.cuda.empty_cache()
         line["secondary"] = sec
     if d.world == 1 and not args.no_cpu:  # rank 0 at N=1 only

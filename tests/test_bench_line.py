@@ -94,6 +94,53 @@ def test_emit_line_writes_detail(tmp_path, capsys):
     assert json.load(open(p)) == full
 
 
+def test_plain_line_needs_no_detail_file(capsys):
+    """A plain run's line (no validation, no detail path) compacts and prints; nothing is written."""
+    full = json.load(open(RECORD))
+    for k in ("secondary", "config4_128M_one_gpu", "validated"):
+        full.pop(k, None)
+    full["cpu_baseline"] = None
+    for r in full["per_rank"]:
+        r.pop("validation", None)
+    back = _strict(bench.emit_line(full, None))
+    for k in CONTRACT:
+        assert k in back, k
+    assert back["per_rank"][0]["valid"] is None
+
+
+def test_dump_outputs_keeps_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32, one value per record byte; above DUMP_ROWS records a sorted sample
+    that is the same on every call; the whole array below it."""
+    import numpy as np
+    import torch
+
+    n = bench.DUMP_ROWS + 1000
+    out = torch.from_numpy(np.random.default_rng(1).integers(0, 256, (n, 32), dtype=np.uint8))
+    info = bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    rec, rows = np.load(tmp_path / "a" / "records.npy"), np.load(tmp_path / "a" / "record_rows.npy")
+    assert info["records"] == bench.DUMP_ROWS and info["of"] == n
+    assert rec.dtype == np.float32 and rec.shape == (bench.DUMP_ROWS, 32) and rows.dtype == np.float64
+    assert np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert np.array_equal(rec, out.numpy()[rows.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "record_rows.npy"))
+    assert rec.nbytes + rows.nbytes <= 64 << 20
+    small = bench.dump_outputs(out[:100], str(tmp_path / "c"))
+    assert small["records"] == 100
+    assert np.array_equal(np.load(tmp_path / "c" / "records.npy"), out[:100].numpy().astype(np.float32))
+
+
+def test_full_is_off_by_default(monkeypatch):
+    import sys
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and a.dump_outputs is None and a.detail is None and a.steps == 7
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "d"
+
+
 @pytest.mark.parametrize("limit", [2048, 4096])
 def test_limit_is_honoured(limit):
     full = json.load(open(RECORD))

@@ -26,13 +26,13 @@ for s in "$@"; do
     thash) step pytest_hash 600 python -m pytest tests/test_gpu_flow_hash.py -m gpu -q -rf -x ;;
     troute) step pytest_route 600 python -m pytest tests/test_gpu_route.py -m gpu -q -rf -x ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 900 python bench.py ;;
-    benchq) step benchq 600 python bench.py --no-secondary --cpu-seconds 4 ;;
-    prof)  step prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --no-cpu --steps 20 ;;
-    pmcf)  step pmc_fetch 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 bench.py --no-cpu --steps 10 --warmup 2 ;;
-    pmcw)  step pmc_write 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- python3 bench.py --no-cpu --steps 10 --warmup 2 ;;
+    bench) step bench 900 python bench.py --full ;;
+    benchq) step benchq 600 python bench.py --full --no-secondary --cpu-seconds 4 ;;
+    prof)  step prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --full --no-cpu --steps 20 ;;
+    pmcf)  step pmc_fetch 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 bench.py --full --no-cpu --steps 10 --warmup 2 ;;
+    pmcw)  step pmc_write 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- python3 bench.py --full --no-cpu --steps 10 --warmup 2 ;;
     tune)  step tune 900 python tools/tune.py ;;
-    dist2) step dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 50 --warmup 5 ;;
+    dist2) step dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 50 --warmup 5 --full ;;
     list)  step counters 300 rocprofv3 -L ;;
     kt)    step kt 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o run -- python3 tools/prof_kernels.py ${PK_ARGS:-} ;;
     kfetch) step kfetch 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/kfetch" -o run -- python3 tools/prof_kernels.py ${PK_ARGS:-} ;;
@@ -40,7 +40,7 @@ for s in "$@"; do
     ksq)   step ksq 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_INSTS_LDS GRBM_GUI_ACTIVE GRBM_COUNT --output-format csv -d "$OUT/ksq" -o run -- python3 tools/prof_kernels.py ${PK_ARGS:-} ;;
     tuneq) step tuneq 600 python tools/tune.py --quick ;;
     tstream) step pytest_stream 600 python -u -m pytest tests/test_gpu_stream.py -m gpu -q -rf -x --timeout 120 --timeout-method thread ;;
-    gpus2) step gpus2 600 python bench.py --gpus 2 --steps 50 --warmup 5 --no-secondary --no-cpu ;;
+    gpus2) step gpus2 600 python bench.py --gpus 2 --steps 50 --warmup 5 --full --no-secondary --no-cpu ;;
     tunes) step tune_stream 600 python tools/tune.py --spec imix:-2,570B:-2,128B:-2,1500B:8 ;;
     ringn) step ring_native 600 python tools/bench_ring_native.py --sweep ;;
     ringprof) step ring_prof 600 rocprofv3 --kernel-trace --hip-runtime-trace --stats --output-format csv -d "$OUT/ringprof" -o run -- python3 tools/bench_ring_native.py --iters 500 ${RP_ARGS:-} ;;
