@@ -19,10 +19,44 @@ func RouteBatch(t *C.halo_route_table_t, dRecords unsafe.Pointer, n int, dIds un
 
 // NatKeys is NatWanFlowHash.GetHashCode with NatGetFlowByWan's key normalisation
 // (engine/ipv4_engine.go:471-479, :554-581) for every record, and its bucket in a table of nb
-// buckets (hashmap/hashmap.go:64), so the Go side probes buckets without hashing.
+// buckets (hashmap/hashmap.go:64), for a caller that keeps NatWanFlowTable in Go and probes its
+// buckets without hashing. A NATing interface whose table lives behind halo_nat_table_t does not
+// need it: NatLookupWan / NatLookupLan / NatLookupQuote below hash, probe and fill the ops on the
+// device, and only new flows come back to the host (halo_nat_resolve_misses).
 func NatKeys(dRecords unsafe.Pointer, n int, natType int, dHash, dBucket unsafe.Pointer, nb uint32) error {
 	return halo(C.halo_flow_hash_device((*C.halo_rx_result_t)(dRecords), C.uint32_t(n), C.HALO_FLOW_NAT_WAN,
 		C.uint32_t(natType), (*C.uint64_t)(dHash), C.uint32_t(nb), (*C.uint32_t)(dBucket), nil))
+}
+
+// NatLookupWan is the inbound half of Ipv4RouteForward (engine/ipv4_engine.go:111-130) for every
+// record: CheckNatPortMapping(WanToLan) else NatGetFlowByWan on the device copy of t (synced with
+// halo_nat_sync_device). A hit ORs HALO_TX_NAT_DST into dOps[i].steps, writes dst_ip / dst_port and
+// stamps the flow with now; dVerdict[i] is HALO_NAT_V_*, dRef[i] the flow id or mapping index, and
+// *dMissCount (zeroed by the caller) counts the HALO_NAT_V_MISS records. dSkip (optional) is
+// DeepNat's dApplied.
+func NatLookupWan(t *C.halo_nat_table_t, dRecords unsafe.Pointer, n int, now uint32, dSkip, dOps, dVerdict, dRef,
+	dMissCount unsafe.Pointer) error {
+	return halo(C.halo_nat_lookup_wan_device(t, (*C.halo_rx_result_t)(dRecords), C.uint32_t(n), C.uint32_t(now),
+		(*C.uint8_t)(dSkip), (*C.halo_tx_op_t)(dOps), (*C.uint8_t)(dVerdict), (*C.uint32_t)(dRef),
+		(*C.uint32_t)(dMissCount), nil))
+}
+
+// NatLookupLan is the outbound half (engine/ipv4_engine.go:203-225) on the out-interface's table:
+// CheckNatPortMapping(LanToWan) else NatGetFlowByHash; a hit ORs HALO_TX_NAT_SRC and writes src_ip /
+// src_port. A miss is a new flow: copy the MISS records back and run halo_nat_resolve_misses, which
+// calls NatAddFlow in packet order.
+func NatLookupLan(t *C.halo_nat_table_t, dRecords unsafe.Pointer, n int, now uint32, dSkip, dOps, dVerdict, dRef,
+	dMissCount unsafe.Pointer) error {
+	return halo(C.halo_nat_lookup_lan_device(t, (*C.halo_rx_result_t)(dRecords), C.uint32_t(n), C.uint32_t(now),
+		(*C.uint8_t)(dSkip), (*C.halo_tx_op_t)(dOps), (*C.uint8_t)(dVerdict), (*C.uint32_t)(dRef),
+		(*C.uint32_t)(dMissCount), nil))
+}
+
+// NatLookupQuote is IcmpTtlDeepNat's NatGetFlowByWan (engine/icmp_engine.go:75-82) between DeepNat's
+// two calls: dQuote is what the first call wrote, dNat what the second call reads.
+func NatLookupQuote(t *C.halo_nat_table_t, dQuote unsafe.Pointer, n int, dNat unsafe.Pointer) error {
+	return halo(C.halo_nat_lookup_quote_device(t, (*C.halo_rx_result_t)(dQuote), C.uint32_t(n),
+		(*C.halo_tx_deep_nat_t)(dNat), nil))
 }
 
 // ParseWithNatKeys is the receive parse and NatKeys in one pass over the frames (records equal to
@@ -65,8 +99,8 @@ func BuildBatch(dDesc unsafe.Pointer, n int, dPayload unsafe.Pointer, srcMac []b
 func BuildWorkspace(n int) uint64 { return uint64(C.halo_tx_build_workspace(C.uint32_t(n))) }
 
 // DeepNat is IcmpTtlDeepNat (engine/icmp_engine.go:55-86) for a batch: with dNat == nil it writes
-// the quote records (NatGetFlowByWan's arguments; hash them with NatKeys), then, called again with
-// the lookups' results, rewrites the frames in place.
+// the quote records (NatGetFlowByWan's arguments; look them up with NatLookupQuote), then, called
+// again with the lookups' results, rewrites the frames in place.
 func DeepNat(dFrames, dOffsets, dLens, dNat, dQuote, dApplied unsafe.Pointer, n int) error {
 	return halo(C.halo_tx_icmp_deep_nat_batch_device((*C.uint8_t)(dFrames), (*C.uint32_t)(dOffsets),
 		(*C.uint16_t)(dLens), C.uint32_t(n), (*C.halo_tx_deep_nat_t)(dNat), csumFlag(),

@@ -107,6 +107,16 @@ FLOW_NAT_LAN, FLOW_NAT_WAN = 0, 1        # HALO_FLOW_*
 NAT_SYMMETRIC, NAT_FULL_CONE = 0, 1      # HALO_NAT_* (engine.NatTypeSymmetric / NatTypeFullCone)
 ROUTE_DTYPE = np.dtype([("dst_ip", "<u4"), ("network_mask", "<u4"), ("next_hop", "<u4"), ("netif", "<u4")])
 ROUTE_NONE, ROUTE_PANIC = 0xFFFFFFFF, 0xFFFFFFFE  # HALO_ROUTE_*
+# halo_nat_flow_t (28 bytes), halo_nat_layout_stats_t and the HALO_NAT_V_* verdicts of the NAT lookups
+NAT_FLOW_DTYPE = np.dtype([("remote_ip", "<u4"), ("wan_ip", "<u4"), ("lan_ip", "<u4"), ("last_alive", "<u4"),
+                           ("remote_port", "<u2"), ("wan_port", "<u2"), ("lan_port", "<u2"), ("proto", "u1"),
+                           ("pad", "u1"), ("id", "<u4")])
+assert NAT_FLOW_DTYPE.itemsize == 28
+NAT_LAYOUT_DTYPE = np.dtype([("slots", "<u4"), ("port_mappings", "<u4"), ("entries", "<u4", (2,)),
+                             ("longest_chain", "<u4", (2,)), ("wrapped", "<u4", (2,))])
+NAT_NO_FLOW = 0xFFFFFFFF
+NAT_MAX_PORT_MAPPINGS = 256
+NAT_V_NONE, NAT_V_SKIP, NAT_V_MISS, NAT_V_FLOW, NAT_V_MAPPING, NAT_V_DROP = range(6)
 # halo_rx_ring_scan_t (24 bytes) and HALO_RING_STOP_* / HALO_RING_REGISTER
 RING_SCAN_DTYPE = np.dtype([("n_frames", "<u4"), ("stop", "<u4"), ("end_bytes", "<u8"), ("max_len", "<u4"),
                             ("pad", "<u4")])
@@ -209,6 +219,13 @@ class NetIf(ctypes.Structure):
         return n
 
 
+class NatConfig(ctypes.Structure):
+    """halo_nat_config_t."""
+
+    _fields_ = [("wan_ip", ctypes.c_uint32), ("nat_type", ctypes.c_uint32), ("capacity_log2", ctypes.c_uint32),
+                ("pad", ctypes.c_uint32)]
+
+
 class BatchDesc(ctypes.Structure):
     """halo_rx_batch_desc_t — one batch of halo_rx_parse_batches_device."""
 
@@ -280,6 +297,30 @@ _PROTOS = {
     "halo_route_lookup_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_void_p]),
     "halo_route_lookup_records_device": (ctypes.c_int, [
         ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_void_p]),
+    "halo_nat_table_create": (ctypes.c_int, [ctypes.POINTER(NatConfig), ctypes.POINTER(ctypes.c_void_p)]),
+    "halo_nat_table_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "halo_nat_port_mapping_add": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint16, ctypes.c_uint8]),
+    "halo_nat_add_flow": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint16, ctypes.c_uint16, ctypes.c_uint8,
+        ctypes.c_uint32, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_nat_get_flow_lan": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint16, ctypes.c_uint8, _u8p,
+        ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_nat_get_flow_wan": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint16, ctypes.c_uint8, _u8p,
+        ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_nat_resolve_misses": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p,
+        ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_nat_expire": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_nat_list": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_nat_layout_stats": (ctypes.c_int, [ctypes.c_void_p, _u8p]),
+    "halo_nat_sync_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    **{f"halo_nat_lookup_{d}{c}_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_void_p])
+       for d in ("wan", "lan") for c in ("", "_compact")},
+    "halo_nat_lookup_quote_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_void_p]),
     "halo_rx_shard_multi": (ctypes.c_int, [
         _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(NetIf), _u8p,
         _u8p, _u8p]),

@@ -6,8 +6,16 @@
 //   | proto u8 — NatFlowHash / NatWanFlowHash (engine/ipv4_engine.go:451-479) as NatGetFlowByHash /
 //   NatGetFlowByWan build them (:524-581); hashed by hashcode.GetHashCodeXXH3 (hashcode/xxh3.go,
 //   hashSmall for 9..16 bytes, :62-66: default secret, seed 0).
+//
+// Host code (nat_table.cc, which places the device NAT table's entries) includes this header too,
+// without HIP: the functions are then plain inline C++ and the 64x64 high multiply is a 128-bit one.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define HALO_FLOWKEY_FN __host__ __device__ __forceinline__
+#else
+#define HALO_FLOWKEY_FN inline
+#endif
 #include <stdint.h>
 
 #include "../../include/halo_rx.h"
@@ -19,10 +27,17 @@ namespace flowkey {
 constexpr uint64_t kSecLo = 0x1f67b3b7a4a44072ull ^ 0x78e5c0cc4ee679cbull;
 constexpr uint64_t kSecHi = 0x2172ffcc7dd05a82ull ^ 0x8e2443f7744608b8ull;
 
-__device__ __forceinline__ uint64_t mul_fold64(uint64_t a, uint64_t b) { return (a * b) ^ __umul64hi(a, b); }
+HALO_FLOWKEY_FN uint64_t mul_fold64(uint64_t a, uint64_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (a * b) ^ __umul64hi(a, b);
+#else
+    const unsigned __int128 p = (unsigned __int128)a * b;
+    return (uint64_t)p ^ (uint64_t)(p >> 64);
+#endif
+}
 
 // hashSmall for 9..16 bytes (xxh3.go:62-66) given the two overlapping 8-byte words
-__device__ __forceinline__ uint64_t hash_9to16(uint64_t w_lo, uint64_t w_hi, uint32_t len) {
+HALO_FLOWKEY_FN uint64_t hash_9to16(uint64_t w_lo, uint64_t w_hi, uint32_t len) {
     const uint64_t lo = w_lo ^ kSecLo, hi = w_hi ^ kSecHi;
     uint64_t v = (uint64_t)len + __builtin_bswap64(lo) + hi + mul_fold64(lo, hi);
     v ^= v >> 37;  // avalanche (xxh3.go:238-243)
@@ -30,20 +45,36 @@ __device__ __forceinline__ uint64_t hash_9to16(uint64_t w_lo, uint64_t w_hi, uin
     return v ^ (v >> 32);
 }
 
-// The flow key of a record (proto, IpAddrToU src/dst, ports as NatGetSrcDstPort gives them) and
-// its hash. kind: HALO_FLOW_NAT_LAN / HALO_FLOW_NAT_WAN; nat_type: HALO_NAT_SYMMETRIC or other.
-__device__ __forceinline__ uint64_t nat_hash(uint32_t proto, uint32_t src, uint32_t dst, uint32_t sport,
-                                             uint32_t dport, uint32_t kind, uint32_t nat_type) {
+// The normalised flow key: the five fields of NatFlowHash / NatWanFlowHash (ports and proto widened).
+struct Key {
+    uint32_t rip, rport, lip, lport, proto;
+};
+
+// XXH3-64 of the 13-byte little-endian image of a key (GetHashCode, engine/ipv4_engine.go:451-479)
+HALO_FLOWKEY_FN uint64_t key_hash(const Key& k) {
+    const uint64_t w_lo = (uint64_t)k.rip | (uint64_t)k.rport << 32 | (uint64_t)(k.lip & 0xFFFFu) << 48;
+    const uint64_t w_hi = (uint64_t)(k.rport >> 8) | (uint64_t)k.lip << 8 | (uint64_t)k.lport << 40 |
+                          (uint64_t)k.proto << 56;  // key bytes 5..12
+    return hash_9to16(w_lo, w_hi, 13);
+}
+
+// The flow key of a record (proto, IpAddrToU src/dst, ports as NatGetSrcDstPort gives them).
+// kind: HALO_FLOW_NAT_LAN / HALO_FLOW_NAT_WAN; nat_type: HALO_NAT_SYMMETRIC or other.
+HALO_FLOWKEY_FN Key nat_key(uint32_t proto, uint32_t src, uint32_t dst, uint32_t sport, uint32_t dport,
+                            uint32_t kind, uint32_t nat_type) {
     const bool wan = kind == HALO_FLOW_NAT_WAN;
     // NatGetFlowByWan(src, sport, dst, dport) / NatGetFlowByHash(dst, dport, src, sport)
     uint32_t rip = wan ? src : dst, rport = wan ? sport : dport;
     const uint32_t lip = wan ? dst : src, lport = wan ? dport : sport;
     if (nat_type != HALO_NAT_SYMMETRIC) { rip = 0; rport = 0; }  // :528-534
     if (proto == 1u) rport = 0;                                    // ICMP, :535-537
-    const uint64_t w_lo = (uint64_t)rip | (uint64_t)rport << 32 | (uint64_t)(lip & 0xFFFFu) << 48;
-    const uint64_t w_hi = (uint64_t)(rport >> 8) | (uint64_t)lip << 8 | (uint64_t)lport << 40 |
-                          (uint64_t)proto << 56;  // key bytes 5..12
-    return hash_9to16(w_lo, w_hi, 13);
+    return Key{rip, rport, lip, lport, proto};
+}
+
+// ... and its hash
+HALO_FLOWKEY_FN uint64_t nat_hash(uint32_t proto, uint32_t src, uint32_t dst, uint32_t sport,
+                                  uint32_t dport, uint32_t kind, uint32_t nat_type) {
+    return key_hash(nat_key(proto, src, dst, sport, dport, kind, nat_type));
 }
 
 }  // namespace flowkey

@@ -1,0 +1,421 @@
+// nat_lookup.hip — the device copy of a NAT flow table (nat_table.cc is its host control plane)
+// and the batched lookups of the forward path on gfx950: the inbound DNAT and outbound SNAT halves
+// of Ipv4RouteForward (engine/ipv4_engine.go:111-130, :203-225) and IcmpTtlDeepNat's
+// NatGetFlowByWan (engine/icmp_engine.go:75-82).
+//
+// Layout: per index (NatFlowTable, NatWanFlowTable) a power-of-two array of 32-byte slots — the
+// whole 13-byte key in the first 16 bytes (remote ip, local ip, both ports, used | proto), then
+// the translation and the flow id — placed by linear probing from XXH3-64(key) & mask, the hash of
+// flow_key.h the host compile and the kernel share. A lookup compares whole keys (HashMap.Get
+// does, hashmap/hashmap.go:63-80) and ends at the first empty slot; tables are rebuilt from
+// scratch by every sync, so there are no tombstones. Two generations, published with
+// release/acquire, under route_lpm.hip's discipline. LastAliveTime is one u32 per flow id in a
+// stamp array both generations share.
+//
+// Kernel shape: one lane per record, grid-stride by whole wavefronts; a probe reads one aligned
+// 32-byte slot (two 16-byte loads of one 32-byte sector); the port-mapping list (<= 256 entries,
+// first match wins) is staged in LDS once per block and scanned there — every lane reads the same
+// address, a broadcast; misses are counted per wavefront with a ballot and one atomic add.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <new>
+#include <shared_mutex>
+#include <vector>
+
+#include "flow_key.h"
+#include "halo_common.h"
+#include "nat_table.h"
+
+namespace halo {
+namespace {
+
+using nat::MapWord;
+using nat::Slot;
+
+struct NatView {
+    const Slot* index[2];  // [HALO_FLOW_NAT_LAN], [HALO_FLOW_NAT_WAN]
+    const MapWord* maps;
+    uint32_t* stamps;
+    uint32_t mask;    // slots - 1
+    uint32_t n_maps;  // <= HALO_NAT_MAX_PORT_MAPPINGS
+    uint32_t nat_type;
+    uint32_t wan_ip;
+};
+
+struct NatDevice {
+    struct Gen {
+        Slot* d_index[2] = {nullptr, nullptr};
+        size_t cap[2] = {0, 0};
+        MapWord* d_maps = nullptr;  // HALO_NAT_MAX_PORT_MAPPINGS entries
+        uint32_t slots = 0, n_maps = 0;
+    } gen[2];
+    uint32_t* d_stamps = nullptr;  // by flow id; shared by both generations
+    size_t stamps_cap = 0;
+    uint32_t n_stamps = 0;  // ids the device copy knows (next_id at the last sync)
+    int device = -1;
+    std::atomic<int> active{-1};  // published generation, -1 before the first sync
+    // Lookups hold it shared from taking their view until their kernel is enqueued; a sync or a
+    // fold holds it exclusively while it drains the device, reads the stamps back and rewrites
+    // the unpublished generation.
+    std::shared_mutex view_mu;
+};
+
+// One probe sequence: the slot whose key equals (k0..k3), or tag 0 when the chain ends.
+__device__ __forceinline__ bool probe(const Slot* __restrict__ idx, uint32_t mask, const flowkey::Key& k, uint4* hit) {
+    const uint32_t ports = k.rport | k.lport << 16, tag = nat::kSlotUsed | k.proto;
+    uint32_t s = (uint32_t)flowkey::key_hash(k) & mask;
+    for (uint32_t step = 0; step <= mask; ++step) {  // bounded: a full index cannot spin
+        const uint4* p = reinterpret_cast<const uint4*>(idx + s);
+        const uint4 key = p[0];
+        const uint4 val = p[1];
+        if (key.w == 0) return false;
+        if (key.x == k.rip && key.y == k.lip && key.z == ports && key.w == tag) {
+            *hit = val;  // x_ip, x_port, id
+            return true;
+        }
+        s = (s + 1) & mask;
+    }
+    return false;
+}
+
+// KIND: HALO_FLOW_NAT_WAN = inbound half (DNAT), HALO_FLOW_NAT_LAN = outbound half (SNAT)
+template <uint32_t KIND, bool COMPACT>
+__global__ void __launch_bounds__(256) nat_lookup_kernel(const NatView v, const void* __restrict__ recs, uint32_t n,
+                                                         uint32_t now, const uint8_t* __restrict__ skip,
+                                                         halo_tx_op_t* __restrict__ ops, uint8_t* __restrict__ verdict,
+                                                         uint32_t* __restrict__ ref, uint32_t* miss_count) {
+    __shared__ MapWord s_maps[HALO_NAT_MAX_PORT_MAPPINGS];
+    for (uint32_t k = threadIdx.x; k < v.n_maps; k += blockDim.x) s_maps[k] = v.maps[k];
+    __syncthreads();
+    const uint32_t stride = gridDim.x * blockDim.x;
+    uint32_t misses = 0;  // wave-uniform
+    // whole wavefronts iterate together (the bound is on the wave's first record), so the ballot
+    // below sees every lane of the wave
+    for (uint32_t base = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < n; base += stride) {
+        const uint32_t i = base + (threadIdx.x & 63u);
+        bool miss = false;
+        if (i < n) {
+            uint32_t proto, src, dst, ports;
+            if (COMPACT) {
+                const uint4 r = reinterpret_cast<const uint4*>(recs)[i];
+                proto = (r.x >> 16) & 0xFFu, src = r.y, dst = r.z, ports = r.w;
+            } else {
+                const uint4 r = reinterpret_cast<const uint4*>(recs)[2ull * i];
+                proto = r.y & 0xFFu, src = r.z, dst = r.w;
+                ports = reinterpret_cast<const uint32_t*>(recs)[8ull * i + 4];
+            }
+            const uint32_t sport = ports & 0xFFFFu, dport = ports >> 16;
+            uint32_t verd, rf = HALO_NAT_NO_FLOW, x_ip = 0, x_port = 0;
+            if (proto == 0xFFu) {
+                verd = HALO_NAT_V_NONE;
+            } else if (skip && skip[i]) {
+                verd = HALO_NAT_V_SKIP;
+            } else {
+                verd = HALO_NAT_V_MISS;
+                if (proto == 6u || proto == 17u) {  // CheckNatPortMapping (:683-707): first match
+                    for (uint32_t k = 0; k < v.n_maps; ++k) {
+                        const MapWord m = s_maps[k];
+                        const bool match = KIND == HALO_FLOW_NAT_WAN
+                                               ? ((m.ports & 0xFFFFu) == dport && m.proto == proto)
+                                               : (m.lan_ip == src && (m.ports >> 16) == sport && m.proto == proto);
+                        if (match) {
+                            verd = HALO_NAT_V_MAPPING;
+                            rf = k;
+                            x_ip = KIND == HALO_FLOW_NAT_WAN ? m.lan_ip : v.wan_ip;
+                            x_port = KIND == HALO_FLOW_NAT_WAN ? (m.ports >> 16) : (m.ports & 0xFFFFu);
+                            break;
+                        }
+                    }
+                }
+                if (verd == HALO_NAT_V_MISS) {
+                    const flowkey::Key k = flowkey::nat_key(proto, src, dst, sport, dport, KIND, v.nat_type);
+                    uint4 hit;
+                    if (probe(v.index[KIND], v.mask, k, &hit)) {
+                        verd = HALO_NAT_V_FLOW;
+                        x_ip = hit.x, x_port = hit.y, rf = hit.z;
+                        v.stamps[rf] = now;  // LastAliveTime = TimeNow (:125, :219)
+                    } else {
+                        miss = true;
+                    }
+                }
+                if (!miss) {  // only this direction's fields: the caller chains both lookups
+                    halo_tx_op_t* op = ops + i;
+                    if (KIND == HALO_FLOW_NAT_WAN) {
+                        op->steps |= HALO_TX_NAT_DST;
+                        op->dst_port = (uint16_t)x_port;
+                        op->dst_ip = x_ip;
+                    } else {
+                        op->steps |= HALO_TX_NAT_SRC;
+                        op->src_port = (uint16_t)x_port;
+                        op->src_ip = x_ip;
+                    }
+                }
+            }
+            verdict[i] = (uint8_t)verd;
+            ref[i] = rf;
+        }
+        misses += (uint32_t)__popcll(__ballot(miss));
+    }
+    if ((threadIdx.x & 63u) == 0 && misses) atomicAdd(miss_count, misses);
+}
+
+__global__ void __launch_bounds__(256) nat_quote_kernel(const NatView v, const halo_rx_result_t* __restrict__ recs,
+                                                        uint32_t n, halo_tx_deep_nat_t* __restrict__ out) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint4 r = reinterpret_cast<const uint4*>(recs)[2ull * i];
+        const uint32_t ports = reinterpret_cast<const uint32_t*>(recs)[8ull * i + 4];
+        uint2 o = make_uint2(0u, 0u);  // lan_ip | lan_port, found, pad
+        if ((r.x & 0xFFu) == HALO_RX_OK) {
+            // the quote record is laid out so that its WAN key is NatGetFlowByWan's (deep_nat.hip)
+            const flowkey::Key k =
+                flowkey::nat_key(r.y & 0xFFu, r.z, r.w, ports & 0xFFFFu, ports >> 16, HALO_FLOW_NAT_WAN, v.nat_type);
+            uint4 hit;
+            if (probe(v.index[HALO_FLOW_NAT_WAN], v.mask, k, &hit)) o = make_uint2(hit.x, (hit.y & 0xFFFFu) | 1u << 16);
+        }
+        reinterpret_cast<uint2*>(out)[i] = o;
+    }
+}
+
+uint32_t nat_blocks(uint64_t threads) {
+    const uint64_t b = (threads + 255) / 256;
+    const uint64_t kMax = 256ull * 8 * 8;
+    return (uint32_t)(b > kMax ? kMax : (b ? b : 1));
+}
+
+template <typename T>
+int grow(T*& p, size_t& cap, size_t need) {
+    if (need <= cap) return HALO_OK;
+    size_t c = cap ? cap : 256;
+    while (c < need) c *= 2;
+    T* q = nullptr;
+    if (hipMalloc(&q, c * sizeof(T)) != hipSuccess) return HALO_E_NOMEM;
+    if (p) (void)hipFree(p);
+    p = q;
+    cap = c;
+    return HALO_OK;
+}
+
+struct DeviceScope {  // run on `dev`, restore the caller's current device
+    int prev = -1;
+    explicit DeviceScope(int dev) {
+        (void)hipGetDevice(&prev);
+        if (prev != dev) (void)hipSetDevice(dev);
+    }
+    ~DeviceScope() {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+NatDevice* dev_of(const halo_nat_table* t) { return static_cast<NatDevice*>(t->dev.load(std::memory_order_acquire)); }
+
+// Drain the device and merge the stamps it wrote into the host table. view_mu held exclusively.
+int fold_locked(halo_nat_table* t, NatDevice* d) {
+    if (d->active.load(std::memory_order_acquire) < 0) return HALO_OK;
+    if (drain_device(d->device) != HALO_OK) return HALO_E_HIP;
+    if (d->n_stamps == 0) return HALO_OK;
+    std::vector<uint32_t> back(d->n_stamps);
+    if (hipMemcpy(back.data(), d->d_stamps, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return HALO_E_HIP;
+    nat::merge_stamps(*t, back.data(), d->n_stamps);
+    return HALO_OK;
+}
+
+// Compile the host table into the unpublished generation and publish it. The caller holds
+// t->sync_mu and view_mu exclusively, runs on d->device under a ParkResidents, and has folded.
+int publish_locked(halo_nat_table* t, NatDevice* d) {
+    nat::Image img;
+    int rc = nat::compile(*t, &img, true);
+    if (rc) return rc;
+    const int cur = d->active.load(std::memory_order_acquire);
+    // the generation written now was last published before `cur`: lookups launched while it was
+    // active may still be running on any stream of the device, so drain the device first
+    if (cur >= 0 && drain_device(d->device) != HALO_OK) return HALO_E_HIP;
+    auto& g = d->gen[cur < 0 ? 0 : 1 - cur];
+    for (int k = 0; k < 2; ++k)
+        if ((rc = grow(g.d_index[k], g.cap[k], img.slots))) return rc;
+    if (!g.d_maps && hipMalloc(&g.d_maps, HALO_NAT_MAX_PORT_MAPPINGS * sizeof(MapWord)) != hipSuccess) return HALO_E_NOMEM;
+    // the stamp array is shared: growing it replaces it for both generations, which is safe only
+    // because the device is drained and no lookup can take a view (view_mu) until we return
+    if (img.stamps.size() > d->stamps_cap) {
+        if (cur >= 0 && drain_device(d->device) != HALO_OK) return HALO_E_HIP;
+        if ((rc = grow(d->d_stamps, d->stamps_cap, img.stamps.size()))) return rc;
+    } else if (!d->d_stamps && (rc = grow(d->d_stamps, d->stamps_cap, 1))) {
+        return rc;
+    }
+    for (int k = 0; k < 2; ++k)
+        if (hipMemcpy(g.d_index[k], img.index[k].data(), (size_t)img.slots * sizeof(Slot), hipMemcpyHostToDevice) != hipSuccess)
+            return HALO_E_HIP;
+    if (!img.maps.empty() &&
+        hipMemcpy(g.d_maps, img.maps.data(), img.maps.size() * sizeof(MapWord), hipMemcpyHostToDevice) != hipSuccess)
+        return HALO_E_HIP;
+    // every live flow's merged stamp (the fold ran under the same lock, so nothing newer exists on
+    // the device); a new flow's slot thereby starts from its host stamp
+    if (!img.stamps.empty() &&
+        hipMemcpy(d->d_stamps, img.stamps.data(), img.stamps.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+        return HALO_E_HIP;
+    g.slots = img.slots;
+    g.n_maps = (uint32_t)img.maps.size();
+    d->n_stamps = (uint32_t)img.stamps.size();
+    // hipMemcpy from pageable memory returns once the host buffer is consumed, not when the copy
+    // has landed: wait for it before publishing
+    if (drain_device(d->device) != HALO_OK) return HALO_E_HIP;
+    d->active.store(cur < 0 ? 0 : 1 - cur, std::memory_order_release);
+    return HALO_OK;
+}
+
+int ops_fold(halo_nat_table* t) {  // halo_nat_expire, t->sync_mu held
+    NatDevice* d = dev_of(t);
+    DeviceScope ds(d->device);
+    ParkResidents park(d->device);
+    std::unique_lock<std::shared_mutex> vl(d->view_mu);
+    return fold_locked(t, d);
+}
+
+int ops_publish(halo_nat_table* t) {  // halo_nat_expire after it removed flows, t->sync_mu held
+    NatDevice* d = dev_of(t);
+    if (d->active.load(std::memory_order_acquire) < 0) return HALO_OK;  // never synced: nothing to rebuild
+    DeviceScope ds(d->device);
+    ParkResidents park(d->device);
+    std::unique_lock<std::shared_mutex> vl(d->view_mu);
+    // again: a lookup enqueued since the fold may have stamped a flow that stays
+    const int rc = fold_locked(t, d);
+    return rc ? rc : publish_locked(t, d);
+}
+
+void ops_destroy(halo_nat_table* t) {
+    NatDevice* d = dev_of(t);
+    if (!d) return;
+    if (d->device >= 0) {
+        DeviceScope ds(d->device);
+        ParkResidents park(d->device);  // through the frees: hipFree waits for every kernel
+        (void)drain_device(d->device);  // no lookup may still read the tables
+        for (auto& g : d->gen) {
+            for (auto* p : g.d_index)
+                if (p) (void)hipFree(p);
+            if (g.d_maps) (void)hipFree(g.d_maps);
+        }
+        if (d->d_stamps) (void)hipFree(d->d_stamps);
+    }
+    delete d;
+    t->dev.store(nullptr, std::memory_order_release);
+}
+
+const nat::DeviceOps kDeviceOps = {ops_fold, ops_publish, ops_destroy};
+
+// The view of the published generation; the caller holds view_mu shared until its launch.
+int nat_view(const halo_nat_table* t, NatDevice* d, NatView* out) {
+    const int a = d->active.load(std::memory_order_acquire);
+    if (a < 0) return HALO_E_INVAL;  // never synced
+    const auto& g = d->gen[a];
+    *out = NatView{{g.d_index[0], g.d_index[1]}, g.d_maps, d->d_stamps, g.slots - 1, g.n_maps, t->cfg.nat_type,
+                   t->cfg.wan_ip};
+    return HALO_OK;
+}
+
+template <uint32_t KIND, bool COMPACT>
+int lookup(const halo_nat_table* t, const void* d_records, uint32_t n, uint32_t now, const uint8_t* d_skip,
+           halo_tx_op_t* d_ops, uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count, halo_stream_t stream) {
+    if (!t) return HALO_E_INVAL;
+    NatDevice* d = dev_of(t);
+    if (!d) return HALO_E_INVAL;  // never synced
+    std::shared_lock<std::shared_mutex> lk(d->view_mu);
+    NatView v;
+    if (nat_view(t, d, &v)) return HALO_E_INVAL;
+    if (!d_verdict || !d_ref || !d_ops || !d_miss_count) return HALO_E_INVAL;
+    if (n == 0) return HALO_OK;
+    if (!d_records) return HALO_E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(d_records) | reinterpret_cast<uintptr_t>(d_ops)) & 15u) return HALO_E_INVAL;
+    if (reinterpret_cast<uintptr_t>(d_ref) & 3u) return HALO_E_INVAL;
+    int rc = check_device();
+    if (rc) return rc;
+    hipLaunchKernelGGL((nat_lookup_kernel<KIND, COMPACT>), dim3(nat_blocks(n)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), v, d_records, n, now, d_skip, d_ops, d_verdict, d_ref,
+                       d_miss_count);
+    return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
+}
+
+}  // namespace
+}  // namespace halo
+
+extern "C" HALO_API int halo_nat_sync_device(halo_nat_table_t* t, int device) {
+    if (!t || device < 0) return HALO_E_INVAL;
+    std::lock_guard<std::mutex> sg(t->sync_mu);
+    halo::NatDevice* d = halo::dev_of(t);
+    if (d && d->device >= 0 && d->device != device) return HALO_E_INVAL;  // one device per table
+    {
+        int cnt = 0;
+        if (hipGetDeviceCount(&cnt) != hipSuccess || device >= cnt) return HALO_E_NODEV;
+    }
+    halo::DeviceScope ds(device);
+    int rc;
+    if ((rc = halo::check_device())) return rc;
+    if (!d) {
+        d = new (std::nothrow) halo::NatDevice;
+        if (!d) return HALO_E_NOMEM;
+        d->device = device;
+        t->dev_ops = &halo::kDeviceOps;
+        t->dev.store(d, std::memory_order_release);
+    }
+    halo::ParkResidents park(device);  // the drains, table growth (hipFree) and copies below
+    std::unique_lock<std::shared_mutex> vl(d->view_mu);  // no lookup between its view and its launch
+    if ((rc = halo::fold_locked(t, d))) return rc;
+    return halo::publish_locked(t, d);
+}
+
+extern "C" HALO_API int halo_nat_lookup_wan_device(const halo_nat_table_t* t, const halo_rx_result_t* d_records,
+                                                   uint32_t n, uint32_t now, const uint8_t* d_skip, halo_tx_op_t* d_ops,
+                                                   uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
+                                                   halo_stream_t stream) {
+    return halo::lookup<HALO_FLOW_NAT_WAN, false>(t, d_records, n, now, d_skip, d_ops, d_verdict, d_ref, d_miss_count,
+                                                  stream);
+}
+
+extern "C" HALO_API int halo_nat_lookup_lan_device(const halo_nat_table_t* t, const halo_rx_result_t* d_records,
+                                                   uint32_t n, uint32_t now, const uint8_t* d_skip, halo_tx_op_t* d_ops,
+                                                   uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
+                                                   halo_stream_t stream) {
+    return halo::lookup<HALO_FLOW_NAT_LAN, false>(t, d_records, n, now, d_skip, d_ops, d_verdict, d_ref, d_miss_count,
+                                                  stream);
+}
+
+extern "C" HALO_API int halo_nat_lookup_wan_compact_device(const halo_nat_table_t* t,
+                                                           const halo_rx_record16_t* d_records, uint32_t n, uint32_t now,
+                                                           const uint8_t* d_skip, halo_tx_op_t* d_ops,
+                                                           uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
+                                                           halo_stream_t stream) {
+    return halo::lookup<HALO_FLOW_NAT_WAN, true>(t, d_records, n, now, d_skip, d_ops, d_verdict, d_ref, d_miss_count,
+                                                 stream);
+}
+
+extern "C" HALO_API int halo_nat_lookup_lan_compact_device(const halo_nat_table_t* t,
+                                                           const halo_rx_record16_t* d_records, uint32_t n, uint32_t now,
+                                                           const uint8_t* d_skip, halo_tx_op_t* d_ops,
+                                                           uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
+                                                           halo_stream_t stream) {
+    return halo::lookup<HALO_FLOW_NAT_LAN, true>(t, d_records, n, now, d_skip, d_ops, d_verdict, d_ref, d_miss_count,
+                                                 stream);
+}
+
+extern "C" HALO_API int halo_nat_lookup_quote_device(const halo_nat_table_t* t, const halo_rx_result_t* d_quote_records,
+                                                     uint32_t n, halo_tx_deep_nat_t* d_nat, halo_stream_t stream) {
+    if (!t) return HALO_E_INVAL;
+    halo::NatDevice* d = halo::dev_of(t);
+    if (!d) return HALO_E_INVAL;  // never synced
+    std::shared_lock<std::shared_mutex> lk(d->view_mu);
+    halo::NatView v;
+    if (halo::nat_view(t, d, &v)) return HALO_E_INVAL;
+    if (!d_nat) return HALO_E_INVAL;
+    if (n == 0) return HALO_OK;
+    if (!d_quote_records) return HALO_E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(d_quote_records) & 15u) || (reinterpret_cast<uintptr_t>(d_nat) & 7u))
+        return HALO_E_INVAL;
+    int rc = halo::check_device();
+    if (rc) return rc;
+    hipLaunchKernelGGL(halo::nat_quote_kernel, dim3(halo::nat_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       v, d_quote_records, n, d_nat);
+    return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
+}

@@ -1,0 +1,344 @@
+// nat_table.cc — the host control plane of the NAT flow table (include/halo_rx.h, "NAT flow
+// table"): NatAddFlow, NatGetFlowByHash / ByWan, CheckNatPortMapping, NatTableClear and ListNat of
+// engine/ipv4_engine.go:524-759 restated over std containers, the slow path for device misses,
+// and the compile of both indexes into the open-addressing image nat_lookup.hip uploads. No HIP.
+#include "nat_table.h"
+
+#include <string.h>
+
+#include <new>
+
+using halo::flowkey::Key;
+using namespace halo::nat;
+
+namespace halo {
+namespace nat {
+
+uint32_t PortSet::take() {
+    // wanPort := 32768; for used { wanPort++; if wanPort == 0 break } (:622-636)
+    for (size_t w = 0; w < 512; ++w) {
+        if (w >= bits.size()) bits.resize(w + 1, 0);
+        const uint64_t free_bits = ~bits[w];
+        if (!free_bits) continue;
+        const uint32_t b = (uint32_t)__builtin_ctzll(free_bits);
+        bits[w] |= 1ull << b;
+        ++used;
+        return 32768u + (uint32_t)w * 64u + b;
+    }
+    return 0;
+}
+
+void PortSet::release(uint32_t port) {
+    if (port < 32768u || port > 65535u) return;
+    const size_t w = (port - 32768u) / 64u;
+    const uint64_t m = 1ull << ((port - 32768u) % 64u);
+    if (w < bits.size() && (bits[w] & m)) {
+        bits[w] &= ~m;
+        --used;
+    }
+}
+
+namespace {
+
+// the normalisation of :525-537 / :555-567 / :588-599
+Key norm_key(const halo_nat_table& t, uint32_t rip, uint32_t rport, uint32_t lip, uint32_t lport, uint32_t proto) {
+    if (t.cfg.nat_type != HALO_NAT_SYMMETRIC) rip = 0, rport = 0;
+    if (proto == 1u) rport = 0;
+    return Key{rip, rport, lip, lport, proto};
+}
+
+const halo_nat_flow_t kNoFlow = {0, 0, 0, 0, 0, 0, 0, 0, 0, HALO_NAT_NO_FLOW};
+
+void report(const Flow* f, halo_nat_flow_t* out, uint32_t* flow_id) {
+    if (out) *out = f ? f->f : kNoFlow;
+    if (flow_id) *flow_id = f ? f->f.id : HALO_NAT_NO_FLOW;
+}
+
+Flow* find(const std::unordered_map<Key, Flow*, KeyHash, KeyEq>& m, const Key& k) {
+    auto it = m.find(k);
+    return it == m.end() ? nullptr : it->second;
+}
+
+// NatAddFlow (:584-680); t.mu held
+Flow* add_flow(halo_nat_table& t, uint32_t lan_ip, uint32_t remote_ip, uint32_t lan_port, uint32_t remote_port,
+               uint32_t proto, uint32_t now) {
+    if (lan_port == 0 || remote_port == 0) return nullptr;
+    if (t.next_id == HALO_NAT_NO_FLOW) return nullptr;  // ids are never reused: the id space is spent
+    const Key lk = norm_key(t, remote_ip, remote_port, lan_ip, lan_port, proto);
+    PortSet& pa = t.ports[lk.rip];
+    const uint32_t wan_port = pa.take();
+    if (wan_port == 0) return nullptr;
+    const uint32_t id = t.next_id++;
+    Flow fl{};
+    fl.f.remote_ip = lk.rip;
+    fl.f.remote_port = (uint16_t)lk.rport;
+    fl.f.wan_ip = t.cfg.wan_ip;
+    fl.f.wan_port = (uint16_t)wan_port;
+    fl.f.lan_ip = lan_ip;
+    fl.f.lan_port = (uint16_t)lan_port;
+    fl.f.proto = (uint8_t)proto;
+    fl.f.last_alive = now;
+    fl.f.id = id;
+    fl.in_lan = true;
+    Flow* p = &t.flows.emplace_hint(t.flows.end(), id, fl)->second;
+    Flow*& slot = t.lan[lk];
+    if (slot) {  // HashMap.Set on an existing key replaces the value: the old flow keeps its WAN key and port
+        slot->in_lan = false;
+        --t.n_lan;
+    }
+    slot = p;
+    ++t.n_lan;
+    t.wan[Key{lk.rip, lk.rport, t.cfg.wan_ip, wan_port, proto}] = p;
+    return p;
+}
+
+// CheckNatPortMapping (:683-707): index of the first match, -1 for none
+int check_mapping(const halo_nat_table& t, uint32_t dir, uint32_t ip, uint32_t port, uint32_t proto) {
+    if (proto != 6u && proto != 17u) return -1;
+    for (size_t k = 0; k < t.maps.size(); ++k) {
+        const PortMapping& e = t.maps[k];
+        if (dir == HALO_FLOW_NAT_WAN ? (e.wan_port == port && e.proto == proto)
+                                     : (e.lan_ip == ip && e.lan_port == port && e.proto == proto))
+            return (int)k;
+    }
+    return -1;
+}
+
+inline bool later(uint32_t a, uint32_t b) { return (int32_t)(a - b) > 0; }
+
+void place(std::vector<Slot>& idx, uint32_t mask, const Key& k, uint32_t x_ip, uint32_t x_port, uint32_t id,
+           uint32_t* longest, uint32_t* wrapped) {
+    const uint32_t home = home_slot(k, mask);
+    uint32_t s = home, chain = 1;
+    while (idx[s].tag) {
+        s = (s + 1) & mask;
+        ++chain;
+    }
+    idx[s] = Slot{k.rip, k.lip, k.rport | k.lport << 16, kSlotUsed | k.proto, x_ip, x_port, id, 0};
+    if (chain > *longest) *longest = chain;
+    if (s < home) ++*wrapped;
+}
+
+}  // namespace
+
+int compile(const halo_nat_table& t, Image* out, bool with_stamps) {
+    std::lock_guard<std::mutex> g(t.mu);
+    const uint32_t n_lan = t.n_lan, n_wan = (uint32_t)t.wan.size();
+    const uint32_t most = n_lan > n_wan ? n_lan : n_wan;
+    uint32_t log2 = t.cfg.capacity_log2;
+    if (log2 == 0) {
+        log2 = 4;  // load <= 0.5
+        while (log2 < 31 && (1ull << log2) < 2ull * most) ++log2;
+        if (log2 > 28) return HALO_E_RANGE;
+    } else if (most >= (1u << log2)) {
+        return HALO_E_RANGE;  // a probe chain must end at an empty slot
+    }
+    out->slots = 1u << log2;
+    const uint32_t mask = out->slots - 1;
+    halo_nat_layout_stats_t st{};
+    st.slots = out->slots;
+    st.port_mappings = (uint32_t)t.maps.size();
+    for (auto& v : out->index) v.assign(out->slots, Slot{});
+    for (const auto& kv : t.flows) {  // ascending id: the layout depends on the table's history only
+        const halo_nat_flow_t& f = kv.second.f;
+        if (kv.second.in_lan) {
+            place(out->index[HALO_FLOW_NAT_LAN], mask, Key{f.remote_ip, f.remote_port, f.lan_ip, f.lan_port, f.proto},
+                  f.wan_ip, f.wan_port, f.id, &st.longest_chain[0], &st.wrapped[0]);
+            ++st.entries[0];
+        }
+        place(out->index[HALO_FLOW_NAT_WAN], mask, Key{f.remote_ip, f.remote_port, f.wan_ip, f.wan_port, f.proto},
+              f.lan_ip, f.lan_port, f.id, &st.longest_chain[1], &st.wrapped[1]);
+        ++st.entries[1];
+    }
+    out->maps.clear();
+    for (const PortMapping& e : t.maps)
+        out->maps.push_back(MapWord{(uint32_t)e.wan_port | (uint32_t)e.lan_port << 16, e.lan_ip, e.proto});
+    out->stamps.clear();
+    if (with_stamps) {
+        out->stamps.assign(t.next_id, 0u);
+        for (const auto& kv : t.flows) out->stamps[kv.first] = kv.second.f.last_alive;
+    }
+    out->stats = st;
+    return HALO_OK;
+}
+
+void merge_stamps(halo_nat_table& t, const uint32_t* dev, uint32_t n) {
+    std::lock_guard<std::mutex> g(t.mu);
+    for (auto& kv : t.flows) {
+        if (kv.first >= n) break;
+        if (later(dev[kv.first], kv.second.f.last_alive)) kv.second.f.last_alive = dev[kv.first];
+    }
+}
+
+}  // namespace nat
+}  // namespace halo
+
+extern "C" HALO_API int halo_nat_table_create(const halo_nat_config_t* cfg, halo_nat_table_t** out) {
+    if (!cfg || !out) return HALO_E_INVAL;
+    if (cfg->capacity_log2 > 28) return HALO_E_RANGE;
+    auto* t = new (std::nothrow) halo_nat_table;
+    if (!t) return HALO_E_NOMEM;
+    t->cfg = *cfg;
+    *out = t;
+    return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_table_destroy(halo_nat_table_t* t) {
+    if (!t) return HALO_E_INVAL;
+    if (t->dev_ops) t->dev_ops->destroy(t);
+    delete t;
+    return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_port_mapping_add(halo_nat_table_t* t, uint16_t wan_port, uint32_t lan_ip,
+                                                  uint16_t lan_port, uint8_t proto) {
+    if (!t) return HALO_E_INVAL;
+    std::lock_guard<std::mutex> g(t->mu);
+    if (t->maps.size() >= HALO_NAT_MAX_PORT_MAPPINGS) return HALO_E_RANGE;
+    t->maps.push_back(PortMapping{wan_port, lan_port, lan_ip, proto});
+    return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_add_flow(halo_nat_table_t* t, uint32_t lan_ip, uint32_t remote_ip, uint16_t lan_port,
+                                          uint16_t remote_port, uint8_t proto, uint32_t now, halo_nat_flow_t* out,
+                                          uint32_t* flow_id) {
+    if (!t) return HALO_E_INVAL;
+    std::lock_guard<std::mutex> g(t->mu);
+    report(add_flow(*t, lan_ip, remote_ip, lan_port, remote_port, proto, now), out, flow_id);
+    return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_get_flow_lan(const halo_nat_table_t* t, uint32_t remote_ip, uint16_t remote_port,
+                                              uint32_t lan_ip, uint16_t lan_port, uint8_t proto, halo_nat_flow_t* out,
+                                              uint32_t* flow_id) {
+    if (!t) return HALO_E_INVAL;
+    std::lock_guard<std::mutex> g(t->mu);
+    report(find(t->lan, norm_key(*t, remote_ip, remote_port, lan_ip, lan_port, proto)), out, flow_id);
+    return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_get_flow_wan(const halo_nat_table_t* t, uint32_t remote_ip, uint16_t remote_port,
+                                              uint32_t wan_ip, uint16_t wan_port, uint8_t proto, halo_nat_flow_t* out,
+                                              uint32_t* flow_id) {
+    if (!t) return HALO_E_INVAL;
+    std::lock_guard<std::mutex> g(t->mu);
+    report(find(t->wan, norm_key(*t, remote_ip, remote_port, wan_ip, wan_port, proto)), out, flow_id);
+    return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_resolve_misses(halo_nat_table_t* t, uint32_t dir, const halo_rx_result_t* records,
+                                                const uint8_t* verdicts, uint32_t n, uint32_t now, halo_tx_op_t* ops,
+                                                uint8_t* verdicts_out, uint32_t* n_added) {
+    if (!t || (dir != HALO_FLOW_NAT_LAN && dir != HALO_FLOW_NAT_WAN)) return HALO_E_INVAL;
+    if (n_added) *n_added = 0;
+    if (n == 0) return HALO_OK;
+    if (!records || !verdicts || !ops || !verdicts_out) return HALO_E_INVAL;
+    const bool wan = dir == HALO_FLOW_NAT_WAN;
+    uint32_t added = 0;
+    std::lock_guard<std::mutex> g(t->mu);
+    for (uint32_t i = 0; i < n; ++i) {  // ascending: NatAddFlow's port depends on packet order
+        const uint8_t v = verdicts[i];
+        verdicts_out[i] = v;
+        if (v != HALO_NAT_V_MISS) continue;
+        const halo_rx_result_t& r = records[i];
+        halo_tx_op_t& op = ops[i];
+        const int m = wan ? check_mapping(*t, dir, 0, r.dport, r.ip_proto) : check_mapping(*t, dir, r.src_ip, r.sport, r.ip_proto);
+        if (m >= 0) {
+            const PortMapping& e = t->maps[(size_t)m];
+            if (wan) {
+                op.steps |= HALO_TX_NAT_DST;
+                op.dst_ip = e.lan_ip;
+                op.dst_port = e.lan_port;
+            } else {
+                op.steps |= HALO_TX_NAT_SRC;
+                op.src_ip = t->cfg.wan_ip;
+                op.src_port = e.wan_port;
+            }
+            verdicts_out[i] = HALO_NAT_V_MAPPING;
+            continue;
+        }
+        Flow* f;
+        if (wan) {
+            f = find(t->wan, norm_key(*t, r.src_ip, r.sport, r.dst_ip, r.dport, r.ip_proto));
+            if (!f) continue;  // stays MISS: local delivery (:120-124)
+        } else {
+            f = find(t->lan, norm_key(*t, r.dst_ip, r.dport, r.src_ip, r.sport, r.ip_proto));
+            if (!f) {
+                f = add_flow(*t, r.src_ip, r.dst_ip, r.sport, r.dport, r.ip_proto, now);
+                if (!f) {
+                    verdicts_out[i] = HALO_NAT_V_DROP;  // :214-217
+                    continue;
+                }
+                ++added;
+            }
+        }
+        f->f.last_alive = now;
+        if (wan) {
+            op.steps |= HALO_TX_NAT_DST;
+            op.dst_ip = f->f.lan_ip;
+            op.dst_port = f->f.lan_port;
+        } else {
+            op.steps |= HALO_TX_NAT_SRC;
+            op.src_ip = f->f.wan_ip;
+            op.src_port = f->f.wan_port;
+        }
+        verdicts_out[i] = HALO_NAT_V_FLOW;
+    }
+    if (n_added) *n_added = added;
+    return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_expire(halo_nat_table_t* t, uint32_t now, uint32_t* n_removed) {
+    if (!t) return HALO_E_INVAL;
+    if (n_removed) *n_removed = 0;
+    std::lock_guard<std::mutex> sg(t->sync_mu);
+    int rc;
+    if (t->dev_ops && (rc = t->dev_ops->fold(t))) return rc;
+    uint32_t removed = 0;
+    {
+        std::lock_guard<std::mutex> g(t->mu);
+        for (auto it = t->flows.begin(); it != t->flows.end();) {
+            Flow& fl = it->second;
+            if (!fl.in_lan || (uint32_t)(now - fl.f.last_alive) <= 60u) {  // NatFlowTable.For (:731-732)
+                ++it;
+                continue;
+            }
+            const halo_nat_flow_t& f = fl.f;
+            t->lan.erase(Key{f.remote_ip, f.remote_port, f.lan_ip, f.lan_port, f.proto});
+            t->wan.erase(Key{f.remote_ip, f.remote_port, f.wan_ip, f.wan_port, f.proto});
+            --t->n_lan;
+            auto pa = t->ports.find(f.remote_ip);
+            if (pa != t->ports.end()) {
+                pa->second.release(f.wan_port);
+                if (pa->second.used == 0) t->ports.erase(pa);  // :748-752
+            }
+            it = t->flows.erase(it);
+            ++removed;
+        }
+    }
+    if (n_removed) *n_removed = removed;
+    if (removed && t->dev_ops && (rc = t->dev_ops->publish(t))) return rc;
+    return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_list(const halo_nat_table_t* t, halo_nat_flow_t* out, uint32_t cap, uint32_t* n) {
+    if (!t || !n || (cap && !out)) return HALO_E_INVAL;
+    std::lock_guard<std::mutex> g(t->mu);
+    uint32_t k = 0;
+    for (const auto& kv : t->flows) {
+        if (!kv.second.in_lan) continue;
+        if (k < cap) out[k] = kv.second.f;
+        ++k;
+    }
+    *n = k;
+    return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_layout_stats(const halo_nat_table_t* t, halo_nat_layout_stats_t* out) {
+    if (!t || !out) return HALO_E_INVAL;
+    Image img;
+    const int rc = compile(*t, &img, false);
+    if (rc) return rc;
+    *out = img.stats;
+    return HALO_OK;
+}

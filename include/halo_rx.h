@@ -510,7 +510,8 @@ HALO_API int halo_tx_fixup_batch_device(uint8_t* d_bytes, const uint32_t* d_offs
  * its src port, quoted proto) and, when a flow exists, rewrites the quote's source to the flow's
  * LAN host (NatChangeSrc on the quote, with its ReCalc* — TCP's needs 38 quoted bytes) and the
  * message's destination to the LAN host with "port" 0 (NatChangeDst on the untrimmed Ethernet
- * payload: its ICMP checksum covers Ethernet padding). The NAT table stays the caller's: call
+ * payload: its ICMP checksum covers Ethernet padding). The lookup is not part of this call
+ * (halo_nat_lookup_quote_device does it on the device, or the caller on its own table): call
  * once with d_nat = NULL to get per frame a quote record — status HALO_RX_OK when the message
  * qualifies, else the failing rx status, HALO_RX_IP_PROTO (not ICMP), HALO_RX_ICMP_TYPE (not
  * ICMP_TTL) or HALO_RX_L4_LEN (quote < 28 B); ip_proto = the quoted protocol; src_ip / sport =
@@ -685,6 +686,157 @@ HALO_API int halo_rx_parse_route_batch_device(const uint8_t* d_bytes, const uint
                                               halo_rx_result_t* d_out, uint32_t* d_status_hist,
                                               const halo_route_table_t* table, uint32_t* d_route_ids,
                                               halo_stream_t stream);
+
+/* ---- NAT flow table (the table between the hash, the route and the rewrite) ------------------
+ * A NATing NetIf's NatFlowTable / NatWanFlowTable / NatPortAlloc / NatPortMappingTable
+ * (engine/ipv4_engine.go:423-759). The control plane stays on the host exactly as the reference
+ * builds it (NatAddFlow's port allocation included) and is the authority; halo_nat_sync_device
+ * compiles both indexes and the port-mapping list into open-addressing tables in HBM, and the
+ * lookups of Ipv4RouteForward's inbound (:111-130) and outbound (:203-225) halves and of
+ * IcmpTtlDeepNat (engine/icmp_engine.go:55-86) run on the GPU over the parsed records, writing the
+ * halo_tx_op_t array halo_tx_fixup_batch_device consumes. Only new flows (device MISS) take the
+ * host slow path, halo_nat_resolve_misses. One table per NATing NetIf. All addresses are in
+ * IpAddrToU form. Not covered: the router-global NatPortMappingFlowTable (:160-186, :238-266) and
+ * ARP, which stay the caller's.
+ *
+ * Flow ids identify NatFlow objects: each NatAddFlow gets a fresh id, never reused, so that an id
+ * read from a device table that is one generation old still names the same flow. LastAliveTime
+ * lives in a u32 stamp array in HBM indexed by flow id, shared by both device generations: a
+ * device hit stores `now` there (plain store; concurrent streams with different `now` are last
+ * writer wins, as the unlocked Go field is), halo_nat_expire and halo_nat_sync_device copy the
+ * array back, and the merged stamp is the later of the host's and the device's in serial-number
+ * order ((int32_t)(a - b) > 0): the true last touch whenever TimeNow does not go backwards.     */
+typedef struct halo_nat_table halo_nat_table_t;
+typedef struct halo_nat_config {
+    uint32_t wan_ip;        /* IpAddrToU(NetIf.IpAddr): NatFlow.WanIpAddr and the mapping SNAT address */
+    uint32_t nat_type;      /* HALO_NAT_SYMMETRIC / HALO_NAT_FULL_CONE (NetIfConfig.NatType)          */
+    uint32_t capacity_log2; /* 0: automatic (load <= 0.5); else the device tables have exactly
+                               2^capacity_log2 slots (<= 28; tests). An index that does not fit
+                               (entries >= slots) makes sync / layout_stats return HALO_E_RANGE   */
+    uint32_t pad;
+} halo_nat_config_t;
+typedef struct halo_nat_flow { /* engine.NatFlow (:429-439) */
+    uint32_t remote_ip;   /* RemoteIpAddr (normalised: 0 unless symmetric)   */
+    uint32_t wan_ip;      /* WanIpAddr                                        */
+    uint32_t lan_ip;      /* LanHostIpAddr                                    */
+    uint32_t last_alive;  /* LastAliveTime (host copy; device stamps are folded in by expire / sync) */
+    uint16_t remote_port; /* RemotePort (normalised: 0 unless symmetric; 0 for ICMP)                  */
+    uint16_t wan_port;    /* WanPort                                          */
+    uint16_t lan_port;    /* LanHostPort                                      */
+    uint8_t proto;        /* Ipv4HeadProto                                    */
+    uint8_t pad;
+    uint32_t id;          /* the flow id (HALO_NAT_NO_FLOW: nil)              */
+} halo_nat_flow_t;        /* 28 B */
+#define HALO_NAT_NO_FLOW 0xFFFFFFFFu
+#define HALO_NAT_MAX_PORT_MAPPINGS 256u
+/* per-record verdict of a lookup */
+#define HALO_NAT_V_NONE 0u    /* ip_proto == 0xFF: ParseIpv4Pkt failed, Ipv4RouteForward never runs  */
+#define HALO_NAT_V_SKIP 1u    /* d_skip[i] != 0: IcmpTtlDeepNat applied, the DNAT is skipped (:116)  */
+#define HALO_NAT_V_MISS 2u    /* no mapping, no flow in the device table                              */
+#define HALO_NAT_V_FLOW 3u    /* a NatFlow; ref = flow id                                             */
+#define HALO_NAT_V_MAPPING 4u /* a NatPortMappingEntry; ref = its index in call order                 */
+#define HALO_NAT_V_DROP 5u    /* halo_nat_resolve_misses only: NatAddFlow returned nil (:214-217)     */
+typedef struct halo_nat_layout_stats { /* index 0 = LAN (NatFlowTable), 1 = WAN (NatWanFlowTable) */
+    uint32_t slots;            /* slots per index (a power of two)                               */
+    uint32_t port_mappings;
+    uint32_t entries[2];
+    uint32_t longest_chain[2]; /* most slots any entry's lookup reads (1 = at its home slot)     */
+    uint32_t wrapped[2];       /* entries whose probe chain runs past the last slot to slot 0    */
+} halo_nat_layout_stats_t;
+
+HALO_API int halo_nat_table_create(const halo_nat_config_t* cfg, halo_nat_table_t** out);
+HALO_API int halo_nat_table_destroy(halo_nat_table_t* t);
+/* NatPortMappingTable, appended in call order as InitRouter appends (engine/engine.go:228);
+ * CheckNatPortMapping (:683-707) takes the first match in that order. At most
+ * HALO_NAT_MAX_PORT_MAPPINGS entries (HALO_E_RANGE beyond). */
+HALO_API int halo_nat_port_mapping_add(halo_nat_table_t* t, uint16_t wan_port, uint32_t lan_ip, uint16_t lan_port,
+                                       uint8_t proto);
+/* NatAddFlow (:584-680): nil when lan_port or remote_port is 0; one port allocator per normalised
+ * remote address, ports taken sequentially from 32768, wrapping to 0 = exhausted (nil); both
+ * indexes point at the one flow (an existing LAN key is replaced, as HashMap.Set does);
+ * LastAliveTime = now. nil is out->id = *flow_id = HALO_NAT_NO_FLOW, not a call failure. `out` and
+ * `flow_id` are optional. */
+HALO_API int halo_nat_add_flow(halo_nat_table_t* t, uint32_t lan_ip, uint32_t remote_ip, uint16_t lan_port,
+                               uint16_t remote_port, uint8_t proto, uint32_t now, halo_nat_flow_t* out,
+                               uint32_t* flow_id);
+/* NatGetFlowByHash (:524-551) / NatGetFlowByWan (:554-581) on the authoritative host table: the
+ * key is normalised by the table's nat_type and compared whole (hashmap/hashmap.go:63-80). */
+HALO_API int halo_nat_get_flow_lan(const halo_nat_table_t* t, uint32_t remote_ip, uint16_t remote_port,
+                                   uint32_t lan_ip, uint16_t lan_port, uint8_t proto, halo_nat_flow_t* out,
+                                   uint32_t* flow_id);
+HALO_API int halo_nat_get_flow_wan(const halo_nat_table_t* t, uint32_t remote_ip, uint16_t remote_port,
+                                   uint32_t wan_ip, uint16_t wan_port, uint8_t proto, halo_nat_flow_t* out,
+                                   uint32_t* flow_id);
+/* The slow path for the records a device lookup left as HALO_NAT_V_MISS; host memory only.
+ * dir = HALO_FLOW_NAT_WAN (inbound half) or HALO_FLOW_NAT_LAN (outbound half). Walks the MISS
+ * records in ascending index order (port allocation depends on packet order), repeats the lookup
+ * on the host table (port mapping, then flow) and, for LAN, runs NatAddFlow on a miss; nil becomes
+ * HALO_NAT_V_DROP (:214-217). A WAN miss stays MISS (:120-124). A hit writes the op fields and
+ * verdict the device would have written and stamps the flow with `now`, so results do not depend
+ * on when the device copy was last synced. verdicts_out (may alias verdicts) gets every verdict;
+ * *n_added (optional) the flows added. */
+HALO_API int halo_nat_resolve_misses(halo_nat_table_t* t, uint32_t dir, const halo_rx_result_t* records,
+                                     const uint8_t* verdicts, uint32_t n, uint32_t now, halo_tx_op_t* ops,
+                                     uint8_t* verdicts_out, uint32_t* n_added);
+/* One NatTableClear tick (:723-759): every flow with (uint32_t)(now - LastAliveTime) > 60 leaves
+ * both indexes and frees its port; an allocator left without ports is dropped. The stamps the
+ * device wrote are folded in first (a device drain), so THE CALLER MUST HAVE SYNCHRONISED THE
+ * STREAMS ITS LOOKUPS RAN ON before this call: a lookup still running may stamp a flow after the
+ * fold. When flows were removed and the table has a device copy, the copy is rebuilt and
+ * published before the call returns: no later lookup hits a removed flow. */
+HALO_API int halo_nat_expire(halo_nat_table_t* t, uint32_t now, uint32_t* n_removed);
+/* ListNat (:710-720): up to `cap` flows into `out` (NULL with cap 0 to count), *n = the total.
+ * Order unspecified. */
+HALO_API int halo_nat_list(const halo_nat_table_t* t, halo_nat_flow_t* out, uint32_t cap, uint32_t* n);
+/* The device layout a sync would produce now (host only, no device needed). */
+HALO_API int halo_nat_layout_stats(const halo_nat_table_t* t, halo_nat_layout_stats_t* out);
+/* Compile both indexes and the port mappings into HBM on `device` (one device per table;
+ * synchronous; the caller's current device is restored). Entries are 32-byte slots (the whole
+ * 13-byte key, the translation, the flow id) placed by linear probing from
+ * XXH3-64(key) & (slots - 1) — the hash of halo_flow_hash_device. Double-buffered as
+ * halo_route_sync_device: the device is drained, the stamps are folded into the host table, the
+ * generation not in use is rewritten and then published; a lookup holds the table's read lock
+ * from taking its view until its kernel is enqueued. */
+HALO_API int halo_nat_sync_device(halo_nat_table_t* t, int device);
+/* The inbound half of Ipv4RouteForward (:111-130) for each record: CheckNatPortMapping(WanToLan,
+ * dport, proto) else NatGetFlowByWan(src, sport, dst, dport, proto). Per record:
+ *   ip_proto == 0xFF              -> HALO_NAT_V_NONE, op untouched
+ *   d_skip && d_skip[i] != 0      -> HALO_NAT_V_SKIP, op untouched (d_skip = deep NAT's d_applied)
+ *   hit   -> ops[i].steps |= HALO_TX_NAT_DST; dst_ip / dst_port = the LAN host; no other op field
+ *            is written; d_verdict[i] = HALO_NAT_V_FLOW / _MAPPING; d_ref[i] = flow id / mapping
+ *            index; a flow's stamp = now
+ *   miss  -> HALO_NAT_V_MISS, d_ref[i] = HALO_NAT_NO_FLOW, *d_miss_count += 1 (the caller zeroes it)
+ * Records are used as they are: the caller selects the FORWARD records, as with
+ * halo_flow_hash_device. Records and ops 16-byte aligned. Uses the table last published
+ * (HALO_E_INVAL before the first sync); n == 0 is OK. Asynchronous on `stream`. */
+HALO_API int halo_nat_lookup_wan_device(const halo_nat_table_t* t, const halo_rx_result_t* d_records, uint32_t n,
+                                        uint32_t now, const uint8_t* d_skip, halo_tx_op_t* d_ops,
+                                        uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
+                                        halo_stream_t stream);
+/* The outbound half (:203-225) on this (the out-interface's) table: CheckNatPortMapping(LanToWan,
+ * src, sport, proto) -> NatChangeSrc(wan_ip, entry.WanPort), else NatGetFlowByHash(dst, dport, src,
+ * sport, proto) -> NatChangeSrc(WanIpAddr, WanPort). A hit ORs HALO_TX_NAT_SRC and writes src_ip /
+ * src_port only. A MISS is a new flow: halo_nat_resolve_misses runs NatAddFlow. */
+HALO_API int halo_nat_lookup_lan_device(const halo_nat_table_t* t, const halo_rx_result_t* d_records, uint32_t n,
+                                        uint32_t now, const uint8_t* d_skip, halo_tx_op_t* d_ops,
+                                        uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
+                                        halo_stream_t stream);
+/* The same over compact records. */
+HALO_API int halo_nat_lookup_wan_compact_device(const halo_nat_table_t* t, const halo_rx_record16_t* d_records,
+                                                uint32_t n, uint32_t now, const uint8_t* d_skip,
+                                                halo_tx_op_t* d_ops, uint8_t* d_verdict, uint32_t* d_ref,
+                                                uint32_t* d_miss_count, halo_stream_t stream);
+HALO_API int halo_nat_lookup_lan_compact_device(const halo_nat_table_t* t, const halo_rx_record16_t* d_records,
+                                                uint32_t n, uint32_t now, const uint8_t* d_skip,
+                                                halo_tx_op_t* d_ops, uint8_t* d_verdict, uint32_t* d_ref,
+                                                uint32_t* d_miss_count, halo_stream_t stream);
+/* IcmpTtlDeepNat's NatGetFlowByWan (engine/icmp_engine.go:75-82), between the two passes of
+ * halo_tx_icmp_deep_nat_batch_device and straight from the quote records the first pass writes:
+ * d_nat[i] = {LanHostIpAddr, LanHostPort, found}; found = 0 (and zero fields) where the quote
+ * status is not HALO_RX_OK or no flow exists. No port mapping, no stamp (the reference sets
+ * neither). */
+HALO_API int halo_nat_lookup_quote_device(const halo_nat_table_t* t, const halo_rx_result_t* d_quote_records,
+                                          uint32_t n, halo_tx_deep_nat_t* d_nat, halo_stream_t stream);
 
 /* ---- the reference engine's per-frame decision (engine/ethernet_engine.go:13-31,
  *      engine/ipv4_engine.go:18-47, engine/{udp,tcp,icmp}_engine.go) ------------------ */
