@@ -53,10 +53,48 @@ namespace {
 #ifndef HALO_RX_NT_STORES  // every other record store (measurement knob)
 #define HALO_RX_NT_STORES 0
 #endif
-template <bool NT = (HALO_RX_NT_STORES != 0)>
+// WT: a write-through store at agent scope (global_store_dwordx4 ... sc1): the line goes through
+// the XCD's L2 to memory at once, so the release at the end of the launch finds no dirty record
+// lines to write back before the next dependent launch may start. Only for stores
+// that write whole 128-byte lines from one wave instruction (64 lanes x 16 B), or every partial
+// line would go to memory on its own. Five interleaved rounds each, kernel time, parent against
+// the knob (profiles/r07/):
+//   HALO_RX_LANE_WT_STORES (the two batch lane kernels; never the ring service kernel, whose
+//     hand-off to the host is its own protocol): on. 1M x 64 B 22.28-22.70 -> 21.58-22.01 us,
+//     4M 75.9-77.8 -> 75.1-75.9 us, 16M 281.9-285.1 -> 279.4-280.5 us; HBM writes per 1M launch
+//     33,554,432 B before and after (no partial lines). HALO_RX_LANE_LDS_PAD re-swept with it:
+//     4096 gains 1 % at 1M and loses 1.3 % at 16M, 5120 equals 4608; 4608 stays.
+//   HALO_RX_GROUP_WT_STORES (32 B records of the group kernels and the mix kernel's group passes):
+//     off. 1500 B 276.5-295.0 -> 275.3-293.5 us (overlap); jumbo 5760-5777 -> 5736-5759 us, 0.3 %,
+//     the ranges 1.3 us apart: too small to call.
+//   HALO_RX_STREAM_WT_STORES (the byte-stream kernel, instead of its non-temporal default): off.
+//     570 B 115.7-119.7 -> 120.9-125.7 us, IMIX 1178-1241 -> 1194-1263 us: slower.
+#ifndef HALO_RX_LANE_WT_STORES
+#define HALO_RX_LANE_WT_STORES 1
+#endif
+#ifndef HALO_RX_GROUP_WT_STORES
+#define HALO_RX_GROUP_WT_STORES 0
+#endif
+#ifndef HALO_RX_STREAM_WT_STORES
+#define HALO_RX_STREAM_WT_STORES 0
+#endif
+enum : int { kStorePlain = 0, kStoreNt = 1, kStoreWt = 2 };
+constexpr int kStoreDefault = HALO_RX_NT_STORES ? kStoreNt : kStorePlain;
+constexpr int kStoreLane = HALO_RX_LANE_WT_STORES ? kStoreWt : kStoreDefault;
+constexpr int kStoreGroup = HALO_RX_GROUP_WT_STORES ? kStoreWt : kStoreDefault;
+constexpr int kStoreStream = HALO_RX_STREAM_WT_STORES ? kStoreWt : HALO_RX_STREAM_NT_STORES ? kStoreNt : kStorePlain;
+template <int ST = kStoreDefault>
 __device__ __forceinline__ void store16(uint4* dst, uint4 v) {
-    if constexpr (NT) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    if constexpr (ST == kStoreWt) {
+        // The compiler does not count this store in vmcnt (it can only wait for more, never less)
+        // and does not know the data registers are read after issue: the s_nop keeps the next
+        // instructions from redefining them while the 16-byte store still reads them.
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1"
+                     :
+                     : "v"(dst), "v"((u32x4){v.x, v.y, v.z, v.w})
+                     : "memory");
+    } else if constexpr (ST == kStoreNt) {
         __builtin_nontemporal_store((u32x4){v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4*>(dst));
     } else {
         *dst = v;
@@ -402,7 +440,7 @@ __device__ __forceinline__ void frame_store(const RxParams& p, uint64_t i, bool 
                 if constexpr (G == 1) {
                     if (stage) stage[0] = r16;
                     else reinterpret_cast<uint4*>(p.out)[i] = r16;
-                } else {
+                } else {  // 16 B per group: 64 B rows at G = 16, never write-through
                     reinterpret_cast<uint4*>(p.out)[i] = r16;
                 }
             }
@@ -416,7 +454,10 @@ __device__ __forceinline__ void frame_store(const RxParams& p, uint64_t i, bool 
                 rec[1] = hi;
             } else {  // lane 0 writes bytes 0..15, lane 1 bytes 16..31 (per-component select: no scratch)
                 const bool h1 = gl != 0;
-                rec[gl] = make_uint4(h1 ? hi.x : lo.x, h1 ? hi.y : lo.y, h1 ? hi.z : lo.z, h1 ? hi.w : lo.w);
+                // a wave instruction writes 64/G consecutive records: rows of 128 B (G = 16) to 512 B
+                const uint4 half = make_uint4(h1 ? hi.x : lo.x, h1 ? hi.y : lo.y, h1 ? hi.z : lo.z, h1 ? hi.w : lo.w);
+                if constexpr (kStoreGroup == kStorePlain) rec[gl] = half;
+                else store16<kStoreGroup>(rec + gl, half);
             }
         }
         if (gl == 0 && p.hist) hist.add(v.status);
@@ -669,17 +710,19 @@ __device__ __forceinline__ void group_kernel_body(const RxParams& p) {
 // profiles/r01/probe_store_patterns.log).
 // One wave's window of 64 consecutive frames, a lane each (frames base .. base + 63): parse, stage
 // the 64 records in the wave's LDS (s_rec_w: 128 x 16 B) and store them fully coalesced.
-template <int LAYOUT, int FUSE>
+// ST: the store policy of the 64 records (store16). The default is what the ring service kernel
+// takes; the two batch kernels pass kStoreLane.
+template <int LAYOUT, int FUSE, int ST = kStoreDefault>
 __device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t base, uint32_t lane, FrameState<1>& st,
                                                    uint4* s_rec_w, Hist& hist);
-template <int LAYOUT, int FUSE>
+template <int LAYOUT, int FUSE, int ST = kStoreDefault>
 __device__ __forceinline__ void lane_window(const RxParams& p, uint32_t base, uint32_t lane, uint4* s_rec_w,
                                            Hist& hist) {
     const uint32_t i = base + lane;
     FrameState<1> st;
     frame_meta<LAYOUT>(p, i, i < p.n, st);
     frame_loads<1>(0, st);
-    lane_window_finish<LAYOUT, FUSE>(p, base, lane, st, s_rec_w, hist);
+    lane_window_finish<LAYOUT, FUSE, ST>(p, base, lane, st, s_rec_w, hist);
 }
 
 #ifndef HALO_RX_LANE_WAVES
@@ -711,7 +754,7 @@ __device__ __forceinline__ void lane_window(const RxParams& p, uint32_t base, ui
 #ifndef HALO_RX_LANE_XCD
 #define HALO_RX_LANE_XCD 0
 #endif
-template <int LAYOUT, int FUSE>
+template <int LAYOUT, int FUSE, int ST>
 __device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t base, uint32_t lane, FrameState<1>& st,
                                                    uint4* s_rec_w, Hist& hist) {
     const bool compact = (p.flags & HALO_RX_RECORD_COMPACT) != 0;
@@ -721,11 +764,11 @@ __device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t b
     __builtin_amdgcn_wave_barrier();
     const uint32_t nrec = p.n - base < 64 ? p.n - base : 64;  // records of this wave
     if (compact) {
-        if (lane < nrec) store16(reinterpret_cast<uint4*>(p.out) + base + lane, s_rec_w[lane]);
+        if (lane < nrec) store16<ST>(reinterpret_cast<uint4*>(p.out) + base + lane, s_rec_w[lane]);
     } else {
         uint4* out4 = reinterpret_cast<uint4*>(p.out) + 2ull * base;
-        if (lane < 2 * nrec) store16(out4 + lane, s_rec_w[lane]);
-        if (64 + lane < 2 * nrec) store16(out4 + 64 + lane, s_rec_w[64 + lane]);
+        if (lane < 2 * nrec) store16<ST>(out4 + lane, s_rec_w[lane]);
+        if (64 + lane < 2 * nrec) store16<ST>(out4 + 64 + lane, s_rec_w[64 + lane]);
     }
     __builtin_amdgcn_wave_barrier();
 }
@@ -763,9 +806,9 @@ rx_lane_kernel(const RxParams p) {
         st.frame = nx.frame; st.L = nx.L; st.ndw = nx.ndw;
         frame_loads<1>(0, st);
         frame_meta<LAYOUT>(p, i + nwaves * 64, i + nwaves * 64 < p.n, nx);
-        lane_window_finish<LAYOUT, FUSE>(p, base, lane, st, s_rec[w], hist);
+        lane_window_finish<LAYOUT, FUSE, kStoreLane>(p, base, lane, st, s_rec[w], hist);
 #else
-        lane_window<LAYOUT, FUSE>(p, base, lane, s_rec[w], hist);
+        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist);
 #endif
     }
     flush_hist(p, hist);
@@ -812,7 +855,7 @@ __global__ void __launch_bounds__(HALO_RX_LANE_BLOCK) rx_lane_multi_kernel(const
         p.out = mp.out[b];
         p.n = mp.n[b];
         const uint32_t base = (win - (b ? mp.win_end[b - 1] : 0u)) * 64u;
-        lane_window<LAYOUT, 0>(p, base, lane, s_rec[w], hist);
+        lane_window<LAYOUT, 0, kStoreLane>(p, base, lane, s_rec[w], hist);
     }
     flush_hist(mp.p, hist);
 }
@@ -1419,13 +1462,12 @@ rx_stream_kernel(const RxParams p) {
         frame_store<1, FUSE, L3>(p, i, present, 0, h, v, c, hist, &stage[compact ? lane : 2 * lane]);
         wave_lds_sync();
         const uint32_t nrec = p.n - wbase < 64 ? p.n - wbase : 64;
-        constexpr bool kNt = HALO_RX_STREAM_NT_STORES != 0;
         if (compact) {
-            if (lane < nrec) store16<kNt>(reinterpret_cast<uint4*>(p.out) + wbase + lane, stage[lane]);
+            if (lane < nrec) store16<kStoreStream>(reinterpret_cast<uint4*>(p.out) + wbase + lane, stage[lane]);
         } else {
             uint4* out4 = reinterpret_cast<uint4*>(p.out) + 2ull * wbase;
-            if (lane < 2 * nrec) store16<kNt>(out4 + lane, stage[lane]);
-            if (64 + lane < 2 * nrec) store16<kNt>(out4 + 64 + lane, stage[64 + lane]);
+            if (lane < 2 * nrec) store16<kStoreStream>(out4 + lane, stage[lane]);
+            if (64 + lane < 2 * nrec) store16<kStoreStream>(out4 + 64 + lane, stage[64 + lane]);
         }
         wave_lds_sync();
     }
