@@ -117,6 +117,15 @@ NAT_LAYOUT_DTYPE = np.dtype([("slots", "<u4"), ("port_mappings", "<u4"), ("entri
 NAT_NO_FLOW = 0xFFFFFFFF
 NAT_MAX_PORT_MAPPINGS = 256
 NAT_V_NONE, NAT_V_SKIP, NAT_V_MISS, NAT_V_FLOW, NAT_V_MAPPING, NAT_V_DROP = range(6)
+# the L2 switch: halo_sw_result_t (4 bytes), halo_switch_entry_t (12 bytes), halo_switch_layout_stats_t, HALO_SW_V_*
+SW_RESULT_DTYPE = np.dtype([("verdict", "u1"), ("out_port", "u1"), ("tx_len", "<u2")])
+SW_ENTRY_DTYPE = np.dtype([("mac", "u1", (6,)), ("port", "u1"), ("pad", "u1"), ("create_time", "<u4")])
+assert SW_RESULT_DTYPE.itemsize == 4 and SW_ENTRY_DTYPE.itemsize == 12
+SW_LAYOUT_DTYPE = np.dtype([("slots", "<u4"), ("entries", "<u4"), ("longest_chain", "<u4"), ("wrapped", "<u4")])
+SW_VERDICT_NAMES = ("ETH_LEN", "ETH_TYPE", "SRC_MCAST", "TABLE_FULL", "UNICAST", "FLOOD")
+SW_V = {name: code for code, name in enumerate(SW_VERDICT_NAMES)}
+SW_V_COUNT = len(SW_VERDICT_NAMES)
+SW_MAX_PORTS = 64
 # halo_rx_ring_scan_t (24 bytes) and HALO_RING_STOP_* / HALO_RING_REGISTER
 RING_SCAN_DTYPE = np.dtype([("n_frames", "<u4"), ("stop", "<u4"), ("end_bytes", "<u8"), ("max_len", "<u4"),
                             ("pad", "<u4")])
@@ -226,6 +235,13 @@ class NatConfig(ctypes.Structure):
                 ("pad", ctypes.c_uint32)]
 
 
+class SwitchConfig(ctypes.Structure):
+    """halo_switch_config_t."""
+
+    _fields_ = [("n_ports", ctypes.c_uint32), ("vlan_id", ctypes.c_uint16 * 64), ("capacity", ctypes.c_uint32),
+                ("slots_log2", ctypes.c_uint32), ("max_batch", ctypes.c_uint32), ("device", ctypes.c_int)]
+
+
 class BatchDesc(ctypes.Structure):
     """halo_rx_batch_desc_t — one batch of halo_rx_parse_batches_device."""
 
@@ -321,6 +337,16 @@ _PROTOS = {
         ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_void_p])
        for d in ("wan", "lan") for c in ("", "_compact")},
     "halo_nat_lookup_quote_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_void_p]),
+    "halo_switch_create": (ctypes.c_int, [ctypes.POINTER(SwitchConfig), ctypes.POINTER(ctypes.c_void_p)]),
+    "halo_switch_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "halo_switch_flood_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),
+    "halo_switch_forward": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p,
+        ctypes.c_void_p]),
+    "halo_switch_expire": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_switch_list": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_switch_layout_stats": (ctypes.c_int, [ctypes.c_void_p, _u8p]),
+    "halo_switch_debug_set_epoch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
     "halo_rx_shard_multi": (ctypes.c_int, [
         _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(NetIf), _u8p,
         _u8p, _u8p]),

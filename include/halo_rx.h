@@ -838,6 +838,100 @@ HALO_API int halo_nat_lookup_lan_compact_device(const halo_nat_table_t* t, const
 HALO_API int halo_nat_lookup_quote_device(const halo_nat_table_t* t, const halo_rx_result_t* d_quote_records,
                                           uint32_t n, halo_tx_deep_nat_t* d_nat, halo_stream_t stream);
 
+/* ---- L2 switch: batched MAC learning and forwarding -----------------------------------------
+ * engine.Switch / SwitchPort (engine/ethernet_engine.go:51-163, engine/engine.go:388-505): one MAC
+ * table per switch, n_ports ports with a VlanId each. A batch is the frames ONE port received, in
+ * receive order; frame i is handled exactly as SwitchPort.RxEthernet handles it after frames
+ * 0..i-1 of the batch:
+ *   1. ParseEthFrm: len < 42 || len > 1514 -> ETH_LEN; EtherType not in {0x05DC, 0x0800, 0x0806,
+ *      0x86DD} -> ETH_TYPE. Nothing learned, nothing forwarded.
+ *   2. src[0] & 1 -> SRC_MCAST. Nothing learned, nothing forwarded.
+ *   3. learn: a source not in the table is inserted unless the table holds `capacity` entries
+ *      (the failed MallocType, :79-83: TABLE_FULL, nothing forwarded); the entry's port = the
+ *      ingress port and CreateTime = now, whether it is new or not.
+ *   4. forward: dst in the table -> UNICAST to the entry's port (which may be the ingress port),
+ *      else FLOOD to every other port of the ingress port's VLAN (halo_switch_flood_mask). The
+ *      lookup sees what frames 0..i learned. Age is not checked: only halo_switch_expire removes.
+ *   5. tx_len = BuildEthFrm's length, max(len, 60), for a forwarded frame; 0 for a dropped one.
+ * Only bytes 0-13 of a frame and its length are read. Not covered: copying or padding the frame
+ * bytes to egress buffers, per-egress-port index lists, batches that mix ingress ports, VLAN tags.
+ *
+ * A switch is either a host switch (cfg.device = -1: host pointers, the sequential loop, `stream`
+ * ignored) or a device switch (cfg.device >= 0: device pointers; table, entry count and scratch
+ * live in HBM and halo_switch_forward is asynchronous on `stream` with no host round trip).
+ * ORDERING: calls on one switch are applied in call order. A device switch has ONE scratch set, so
+ * every halo_switch_forward on it must be issued on one stream, or be ordered by the caller;
+ * halo_switch_expire / _list / _layout_stats drain the device first and are synchronous. Calls on
+ * one switch must not run concurrently from several host threads.
+ * FAILURE: argument errors (HALO_E_INVAL / _RANGE) leave the switch as it was. HALO_E_HIP from a
+ * device switch means a runtime call failed after the call had begun to change device state; the
+ * table is then undefined, every later call on the switch returns HALO_E_HIP, and the only valid
+ * call is halo_switch_destroy. */
+typedef struct halo_switch halo_switch_t;
+#define HALO_SW_MAX_PORTS 64u
+typedef struct halo_switch_config {
+    uint32_t n_ports;                    /* 1..64                                                   */
+    uint16_t vlan_id[HALO_SW_MAX_PORTS]; /* SwitchPortConfig.VlanId of ports 0..n_ports-1           */
+    uint32_t capacity;                   /* most MAC entries (the StaticAllocator's room); > 0      */
+    uint32_t slots_log2;                 /* 0: automatic, the next power of two >= 2 * capacity;
+                                            else exactly 2^slots_log2 slots (<= 28; tests force
+                                            collisions with it). slots must exceed capacity         */
+    uint32_t max_batch;                  /* most frames per halo_switch_forward (1..2^24)           */
+    int device;                          /* -1: host mode; else the HIP device of the table         */
+} halo_switch_config_t;
+typedef struct halo_sw_result {
+    uint8_t verdict;   /* HALO_SW_V_*                                  */
+    uint8_t out_port;  /* the egress port of a UNICAST, else 0xFF      */
+    uint16_t tx_len;   /* max(len, 60) when forwarded, else 0          */
+} halo_sw_result_t;    /* 4 B */
+#define HALO_SW_V_ETH_LEN 0u
+#define HALO_SW_V_ETH_TYPE 1u
+#define HALO_SW_V_SRC_MCAST 2u
+#define HALO_SW_V_TABLE_FULL 3u
+#define HALO_SW_V_UNICAST 4u
+#define HALO_SW_V_FLOOD 5u
+#define HALO_SW_V_COUNT 6u
+#define HALO_SW_MAC_AGE 300u /* SwitchMacAddrClear: seconds */
+typedef struct halo_switch_entry { /* engine.SwitchMacAddr */
+    uint8_t mac[6];
+    uint8_t port;          /* NetIf, as the port's index */
+    uint8_t pad;
+    uint32_t create_time;  /* CreateTime                 */
+} halo_switch_entry_t;     /* 12 B */
+typedef struct halo_switch_layout_stats {
+    uint32_t slots;         /* slots of the device table (a power of two)                        */
+    uint32_t entries;
+    uint32_t longest_chain; /* most slots any entry's lookup reads (1 = at its home slot); 0 in host mode */
+    uint32_t wrapped;       /* entries whose probe chain runs past the last slot to slot 0; 0 in host mode */
+} halo_switch_layout_stats_t;
+
+/* HALO_E_INVAL: null pointer, n_ports outside 1..64, capacity 0, slots <= capacity, slots_log2 >
+ * 28, max_batch outside 1..2^24, device < -1. HALO_E_NODEV / _ARCH / _NOMEM as elsewhere. */
+HALO_API int halo_switch_create(const halo_switch_config_t* cfg, halo_switch_t** out);
+HALO_API int halo_switch_destroy(halo_switch_t* sw);
+/* Bit q of *mask: a FLOOD from `port` goes out of port q (q != port, same VlanId). */
+HALO_API int halo_switch_flood_mask(const halo_switch_t* sw, uint32_t port, uint64_t* mask);
+/* One batch from ingress `port` at time `now` (Switch.TimeNow). Frame i is the lens[i] bytes at
+ * bytes + 4 * offsets_dw[i], as halo_rx_parse_batch_device takes them. results[i] gets its verdict
+ * (4-byte aligned); `counts`, if not NULL, is HALO_SW_V_COUNT u32 counters that are INCREMENTED.
+ * HALO_E_INVAL: port >= n_ports, a null array with n > 0. HALO_E_RANGE: n > max_batch. n == 0 is OK. */
+HALO_API int halo_switch_forward(halo_switch_t* sw, uint32_t port, const uint8_t* bytes, const uint32_t* offsets_dw,
+                                 const uint16_t* lens, uint32_t n, uint32_t now, halo_sw_result_t* results,
+                                 uint32_t* counts, halo_stream_t stream);
+/* One SwitchMacAddrClear tick: every entry with now > (uint32_t)(CreateTime + 300) is removed
+ * (the u32 add wraps, as Go's does). Synchronous; the room freed is usable by the next batch.
+ * n_removed is optional. */
+HALO_API int halo_switch_expire(halo_switch_t* sw, uint32_t now, uint32_t* n_removed);
+/* ListSwitchMacAddr: up to `cap` entries into `out` (host memory; NULL with cap 0 to count),
+ * *n = the total. Synchronises. Order unspecified. */
+HALO_API int halo_switch_list(halo_switch_t* sw, halo_switch_entry_t* out, uint32_t cap, uint32_t* n);
+HALO_API int halo_switch_layout_stats(halo_switch_t* sw, halo_switch_layout_stats_t* out);
+/* TESTING ONLY — a device switch tags the entries of its per-call scratch set with a 16-bit call
+ * number and clears the set when that number wraps, once in 65535 calls. This sets the number the
+ * last call is taken to have had (0..65535; synchronous, clears the set), so that a test reaches
+ * the wrap in a few calls. HALO_E_INVAL for a host switch. */
+HALO_API int halo_switch_debug_set_epoch(halo_switch_t* sw, uint32_t epoch);
+
 /* ---- the reference engine's per-frame decision (engine/ethernet_engine.go:13-31,
  *      engine/ipv4_engine.go:18-47, engine/{udp,tcp,icmp}_engine.go) ------------------ */
 typedef enum halo_rx_action {
