@@ -6,7 +6,9 @@ the thin Python host side over that ABI (ctypes). See DESIGN.md.
 """
 from . import _lib  # noqa: F401  (raises if libhalo_rx.so is not built: no CPU fallback)
 from ._lib import ACTION, ACTION_NAMES, RESULT_DTYPE, STATUS, STATUS_NAMES, NetIf, HaloError  # noqa: F401
+from .arp import ArpTable  # noqa: F401
 from .nat import NatTable  # noqa: F401
 from .switch import Switch  # noqa: F401
 
-__all__ = ["ACTION", "ACTION_NAMES", "RESULT_DTYPE", "STATUS", "STATUS_NAMES", "NetIf", "HaloError", "NatTable", "Switch"]
+__all__ = ["ACTION", "ACTION_NAMES", "RESULT_DTYPE", "STATUS", "STATUS_NAMES", "NetIf", "HaloError", "ArpTable", "NatTable",
+           "Switch"]

@@ -126,6 +126,22 @@ SW_VERDICT_NAMES = ("ETH_LEN", "ETH_TYPE", "SRC_MCAST", "TABLE_FULL", "UNICAST",
 SW_V = {name: code for code, name in enumerate(SW_VERDICT_NAMES)}
 SW_V_COUNT = len(SW_VERDICT_NAMES)
 SW_MAX_PORTS = 64
+# the ARP neighbour cache: halo_arp_entry_t (16 bytes), halo_arp_msg_t (40), halo_arp_result_t (8),
+# halo_arp_layout_stats_t, HALO_ARP_H_* / HALO_ARP_GET_* / HALO_ARP_V_*
+ARP_ENTRY_DTYPE = np.dtype([("ip", "<u4"), ("mac", "u1", (6,)), ("netif", "u1"), ("pad", "u1"), ("exp_time", "<u4")])
+ARP_MSG_DTYPE = np.dtype([("index", "<u4"), ("netif", "u1"), ("pad", "u1"), ("eth_src", "u1", (6,)), ("arp", "u1", (28,))])
+ARP_RESULT_DTYPE = np.dtype([("verdict", "u1"), ("out_netif", "u1"), ("tx_len", "<u2"), ("target_ip", "<u4")])
+assert ARP_ENTRY_DTYPE.itemsize == 16 and ARP_MSG_DTYPE.itemsize == 40 and ARP_RESULT_DTYPE.itemsize == 8
+ARP_LAYOUT_DTYPE = np.dtype([("slots", "<u4"), ("entries", "<u4"), ("longest_chain", "<u4"), ("wrapped", "<u4")])
+ARP_H_NAMES = ("BAD_OP", "SRC_MISMATCH", "CONFLICT", "ACCEPTED")
+ARP_H = {name: code for code, name in enumerate(ARP_H_NAMES)}
+ARP_H_MASK, ARP_H_F_NOT_LEARNED, ARP_H_F_REPLY = 0x0F, 0x40, 0x80
+ARP_GET_ABSENT, ARP_GET_FOUND, ARP_GET_OWN_IP = 0, 1, 2
+ARP_VERDICT_NAMES = ("NONE", "NO_ROUTE", "ROUTE_PANIC", "LOOPBACK", "OWN_IP", "MISS", "HIT")
+ARP_V = {name: code for code, name in enumerate(ARP_VERDICT_NAMES)}
+ARP_V_COUNT = len(ARP_VERDICT_NAMES)
+ARP_MAX_NETIFS = 64
+ARP_AGE, ARP_REFRESH_AHEAD = 300, 10
 # halo_rx_ring_scan_t (24 bytes) and HALO_RING_STOP_* / HALO_RING_REGISTER
 RING_SCAN_DTYPE = np.dtype([("n_frames", "<u4"), ("stop", "<u4"), ("end_bytes", "<u8"), ("max_len", "<u4"),
                             ("pad", "<u4")])
@@ -242,6 +258,13 @@ class SwitchConfig(ctypes.Structure):
                 ("slots_log2", ctypes.c_uint32), ("max_batch", ctypes.c_uint32), ("device", ctypes.c_int)]
 
 
+class ArpConfig(ctypes.Structure):
+    """halo_arp_config_t."""
+
+    _fields_ = [("n_netifs", ctypes.c_uint32), ("netif", NetIf * 64), ("capacity", ctypes.c_uint32),
+                ("slots_log2", ctypes.c_uint32)]
+
+
 class BatchDesc(ctypes.Structure):
     """halo_rx_batch_desc_t — one batch of halo_rx_parse_batches_device."""
 
@@ -347,6 +370,31 @@ _PROTOS = {
     "halo_switch_list": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
     "halo_switch_layout_stats": (ctypes.c_int, [ctypes.c_void_p, _u8p]),
     "halo_switch_debug_set_epoch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    "halo_arp_table_create": (ctypes.c_int, [ctypes.POINTER(ArpConfig), ctypes.POINTER(ctypes.c_void_p)]),
+    "halo_arp_table_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "halo_arp_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, _u8p, ctypes.c_uint32]),
+    "halo_arp_get": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_arp_handle_msgs": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint32),
+        ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_arp_build_request": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, _u8p]),
+    "halo_arp_expire": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_arp_refresh_list": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, _u8p, _u8p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_arp_list": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_arp_layout_stats": (ctypes.c_int, [ctypes.c_void_p, _u8p]),
+    "halo_arp_dirty": (ctypes.c_int, [ctypes.c_void_p]),
+    "halo_arp_sync_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "halo_arp_lookup_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.c_void_p]),
+    "halo_arp_encap_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p,
+        ctypes.c_void_p]),
+    "halo_arp_gather_workspace": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "halo_arp_gather_device": (ctypes.c_int, [
+        _u8p, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, _u8p, ctypes.c_uint64,
+        ctypes.c_void_p]),
     "halo_rx_shard_multi": (ctypes.c_int, [
         _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(NetIf), _u8p,
         _u8p, _u8p]),

@@ -696,8 +696,9 @@ HALO_API int halo_rx_parse_route_batch_device(const uint8_t* d_bytes, const uint
  * IcmpTtlDeepNat (engine/icmp_engine.go:55-86) run on the GPU over the parsed records, writing the
  * halo_tx_op_t array halo_tx_fixup_batch_device consumes. Only new flows (device MISS) take the
  * host slow path, halo_nat_resolve_misses. One table per NATing NetIf. All addresses are in
- * IpAddrToU form. Not covered: the router-global NatPortMappingFlowTable (:160-186, :238-266) and
- * ARP, which stay the caller's.
+ * IpAddrToU form. Not covered: the router-global NatPortMappingFlowTable (:160-186, :238-266),
+ * which stays the caller's. The ARP step that follows the rewrite is halo_arp_encap_device ("ARP
+ * neighbour cache" below).
  *
  * Flow ids identify NatFlow objects: each NatAddFlow gets a fresh id, never reused, so that an id
  * read from a device table that is one generation old still names the same flow. LastAliveTime
@@ -931,6 +932,188 @@ HALO_API int halo_switch_layout_stats(halo_switch_t* sw, halo_switch_layout_stat
  * last call is taken to have had (0..65535; synchronous, clears the set), so that a test reaches
  * the wrap in a few calls. HALO_E_INVAL for a host switch. */
 HALO_API int halo_switch_debug_set_epoch(halo_switch_t* sw, uint32_t epoch);
+
+/* ---- ARP neighbour cache: batched next-hop resolve and L2 rewrite ----------------------------
+ * A Router's ARP state (engine/arp_engine.go, protocol/arp.go): up to 64 NetIfs, each with its own
+ * IpAddr and MacAddr, one cache keyed by (netif, ip) and one `capacity` shared by all NetIfs (the
+ * room of the shared StaticAllocator). The host table is the control plane and the authority;
+ * halo_arp_sync_device compiles it into an open-addressing table in HBM, and the last step of
+ * Ipv4RouteForward (engine/ipv4_engine.go:180-201, :226-236, :267) — route id -> (next hop, out
+ * NetIf) -> GetArpCache -> the Ethernet header TxEthernet / BuildEthFrm writes — runs on the GPU
+ * over a device-resident batch, after halo_tx_fixup_batch_device in stream order. A gather kernel
+ * brings a batch's ARP messages to the host in frame order for halo_arp_handle_msgs.
+ *
+ * Reference semantics kept, quirks included. All addresses are in IpAddrToU form.
+ *   SetArpCache (:60-76): an absent key is inserted unless the table holds `capacity` entries (then
+ *     nothing happens, silently); an existing key is always refreshed, also when the table is full;
+ *     ExpTime = (uint32_t)(now + 300); the MAC is not checked (a group MAC is stored).
+ *   GetArpCache (:31-46): ip == the NetIf's own IpAddr -> nil and no request; a present key -> the
+ *     entry whatever its ExpTime (only a clear tick removes); an absent key -> nil, and the caller
+ *     owes one SendArpReq per call (the reference does not deduplicate).
+ *   HandleArp (:79-105), in this order: op (payload bytes 6-7) not 1 or 2 -> BAD_OP (bytes 0-5 are
+ *     never checked); sha != the frame's Ethernet source -> SRC_MISMATCH; spa == own IpAddr ->
+ *     CONFLICT; SetArpCache(spa, sha); a REQUEST whose tpa is the own IpAddr is answered even when
+ *     the table was full; a reply that is not for us still learns.
+ *   ArpTableClear (:129-147): every entry with now > ExpTime goes (plain u32 compare of a value that
+ *     wrapped when stored). ArpTableRefresh (:108-126): one request per entry with
+ *     now > (uint32_t)(ExpTime - 10); the subtraction wraps, so ExpTime < 10 is never refreshed.
+ *
+ * ORDERING: device lookups see the table as of the last halo_arp_sync_device (or the last
+ * halo_arp_expire that removed an entry). An entry learned since is a device MISS — a dropped
+ * packet and a redundant request, what the reference gives a packet that arrives just before the
+ * ARP reply. The engine loop re-syncs when halo_arp_dirty.
+ * FAILURE: argument errors (HALO_E_INVAL / _RANGE) leave the table as it was; a malformed ARP
+ * message is data (its verdict). A library built without the device side answers HALO_E_NODEV to
+ * the *_device calls.
+ * Not covered: halo_tx_build_desc_t.dst_mac of locally originated packets; zero-padding a forwarded
+ * frame to 60 bytes in place (tx_len tells the caller: frames are packed at 4-byte boundaries and
+ * the padding would overwrite a neighbour); per-egress index lists; NatPortMappingFlowTable;
+ * compact records in the gather; DHCP. */
+typedef struct halo_arp_table halo_arp_table_t;
+#define HALO_ARP_MAX_NETIFS 64u
+#define HALO_ARP_AGE 300u          /* SetArpCache: ExpTime = now + 300             */
+#define HALO_ARP_REFRESH_AHEAD 10u /* ArpTableRefresh: now > ExpTime - 10          */
+typedef struct halo_arp_config {
+    uint32_t n_netifs;                          /* 1..64                                                */
+    halo_rx_netif_t netif[HALO_ARP_MAX_NETIFS]; /* NetIfs 0..n_netifs-1: mac, ip and nat_enable are read */
+    uint32_t capacity;                          /* most entries, all NetIfs together; > 0               */
+    uint32_t slots_log2;                        /* 0: automatic, the next power of two >= 2 * capacity;
+                                                   else exactly 2^slots_log2 slots (<= 28; tests force
+                                                   collisions with it). slots must exceed capacity       */
+} halo_arp_config_t;
+typedef struct halo_arp_entry { /* engine.ArpCache, with the NetIf whose table holds it */
+    uint32_t ip;       /* IpAddr  */
+    uint8_t mac[6];    /* MacAddr */
+    uint8_t netif;
+    uint8_t pad;
+    uint32_t exp_time; /* ExpTime */
+} halo_arp_entry_t;    /* 16 B */
+typedef struct halo_arp_msg { /* one received ARP message, as halo_arp_gather_device writes it */
+    uint32_t index;     /* the frame's index in its batch          */
+    uint8_t netif;      /* the NetIf that received it              */
+    uint8_t pad;
+    uint8_t eth_src[6]; /* frame bytes 6-11                         */
+    uint8_t arp[28];    /* frame bytes 14-41, verbatim              */
+} halo_arp_msg_t;       /* 40 B */
+/* halo_arp_handle_msgs verdict byte: one HALO_ARP_H_* code | flag bits */
+#define HALO_ARP_H_BAD_OP 0u
+#define HALO_ARP_H_SRC_MISMATCH 1u
+#define HALO_ARP_H_CONFLICT 2u
+#define HALO_ARP_H_ACCEPTED 3u
+#define HALO_ARP_H_COUNT 4u
+#define HALO_ARP_H_MASK 0x0Fu
+#define HALO_ARP_H_F_NOT_LEARNED 0x40u /* ACCEPTED, but SetArpCache found the table full */
+#define HALO_ARP_H_F_REPLY 0x80u       /* a reply frame was built                         */
+/* halo_arp_get's *found */
+#define HALO_ARP_GET_ABSENT 0u /* nil; the caller owes a SendArpReq          */
+#define HALO_ARP_GET_FOUND 1u
+#define HALO_ARP_GET_OWN_IP 2u /* nil; ip is the NetIf's own, no request     */
+/* verdicts of halo_arp_lookup_device (NONE, OWN_IP, MISS, HIT) and halo_arp_encap_device (all) */
+#define HALO_ARP_V_NONE 0u        /* not selected, not an IPv4 frame of >= 34 bytes, a route id or
+                                     NetIf the device copy does not know: nothing read or written  */
+#define HALO_ARP_V_NO_ROUTE 1u    /* HALO_ROUTE_NONE                                               */
+#define HALO_ARP_V_ROUTE_PANIC 2u /* HALO_ROUTE_PANIC                                              */
+#define HALO_ARP_V_LOOPBACK 3u    /* dst == the out NetIf's IpAddr, in NetIf not NATing (:180-201);
+                                     the LoChan copy is the caller's                               */
+#define HALO_ARP_V_OWN_IP 4u      /* GetArpCache(own IpAddr): nil, no request                      */
+#define HALO_ARP_V_MISS 5u        /* nil: the packet is dropped, one SendArpReq(target_ip) is owed */
+#define HALO_ARP_V_HIT 6u         /* the frame's bytes 0-11 were rewritten                         */
+#define HALO_ARP_V_COUNT 7u
+typedef struct halo_arp_result {
+    uint8_t verdict;    /* HALO_ARP_V_*                                                          */
+    uint8_t out_netif;  /* the route's NetIf (LOOPBACK, OWN_IP, MISS, HIT), else 0xFF            */
+    uint16_t tx_len;    /* BuildEthFrm's length, max(len, 60), on HIT; else 0                    */
+    uint32_t target_ip; /* the address looked up (OWN_IP, MISS, HIT): next hop or dst; else 0    */
+} halo_arp_result_t;    /* 8 B */
+typedef struct halo_arp_layout_stats {
+    uint32_t slots;         /* slots of the device table (a power of two)                          */
+    uint32_t entries;
+    uint32_t longest_chain; /* most slots any entry's lookup reads (1 = at its home slot)          */
+    uint32_t wrapped;       /* entries whose probe chain runs past the last slot to slot 0         */
+} halo_arp_layout_stats_t;
+
+/* HALO_E_INVAL: null pointer, n_netifs outside 1..64, capacity 0, slots <= capacity, slots_log2 > 28. */
+HALO_API int halo_arp_table_create(const halo_arp_config_t* cfg, halo_arp_table_t** out);
+HALO_API int halo_arp_table_destroy(halo_arp_table_t* t);
+/* SetArpCache on NetIf `netif` at time `now` (Router.TimeNow). HALO_E_RANGE: netif >= n_netifs. */
+HALO_API int halo_arp_set(halo_arp_table_t* t, uint32_t netif, uint32_t ip, const uint8_t mac[6], uint32_t now);
+/* GetArpCache on the host table: *found = HALO_ARP_GET_*; *entry (optional) is filled when FOUND. */
+HALO_API int halo_arp_get(const halo_arp_table_t* t, uint32_t netif, uint32_t ip, halo_arp_entry_t* entry,
+                          uint32_t* found);
+/* HandleArp over msgs[0..n) in ascending order at time `now`. verdicts[i] = HALO_ARP_H_* | flags.
+ * The k-th reply built (60 bytes: BuildArpPkt(REPLY, own mac, own ip, sha, spa) inside
+ * BuildEthFrm(dst = sha, src = own mac, 0x0806), zero-padded) goes to reply_frames + 60 * k when
+ * reply_frames is not NULL — only 60 bytes per reply are written, so 60 * n always suffices;
+ * *n_replies counts them either way. *n_changed = inserts + entries whose MAC changed: what makes a re-sync worthwhile.
+ * n_replies / n_changed are optional. HALO_E_RANGE, nothing applied: a msgs[i].netif >= n_netifs. */
+HALO_API int halo_arp_handle_msgs(halo_arp_table_t* t, const halo_arp_msg_t* msgs, uint32_t n, uint32_t now,
+                                  uint8_t* verdicts, uint8_t* reply_frames, uint32_t* n_replies,
+                                  uint32_t* n_changed);
+/* SendArpReq(target_ip) of NetIf `netif`: BuildArpPkt(REQUEST, mac, ip, ff:ff:ff:ff:ff:ff, target)
+ * — the body's target MAC is the broadcast MAC, not zeros — to the Ethernet broadcast, padded to
+ * 60 bytes. target_ip == the NetIf's own ip is SendFreeArp. */
+HALO_API int halo_arp_build_request(const halo_arp_table_t* t, uint32_t netif, uint32_t target_ip, uint8_t out[60]);
+/* One ArpTableClear tick. Synchronous; when it removed an entry and a device copy exists, the copy
+ * is rebuilt and published before the call returns. n_removed is optional. */
+HALO_API int halo_arp_expire(halo_arp_table_t* t, uint32_t now, uint32_t* n_removed);
+/* One ArpTableRefresh tick: the (netif, ip) of up to `cap` entries to SendArpReq for; *n = the total. */
+HALO_API int halo_arp_refresh_list(const halo_arp_table_t* t, uint32_t now, uint8_t* netif_out, uint32_t* ip_out,
+                                   uint32_t cap, uint32_t* n);
+/* ListArp of every NetIf: up to `cap` entries (NULL with cap 0 to count), *n = the total. */
+HALO_API int halo_arp_list(const halo_arp_table_t* t, halo_arp_entry_t* out, uint32_t cap, uint32_t* n);
+/* The layout halo_arp_sync_device would upload now. Host only. */
+HALO_API int halo_arp_layout_stats(const halo_arp_table_t* t, halo_arp_layout_stats_t* out);
+/* 1 when the host table differs from the last published device copy (or none exists): an insert or
+ * a changed MAC since. A refresh of ExpTime alone does not count — the device holds no ExpTime. */
+HALO_API int halo_arp_dirty(const halo_arp_table_t* t);
+
+/* Compile the cache into HBM on `device` and publish it (synchronous): 16-byte slots {ip, used |
+ * netif, mac[0..3], mac[4..5]}, linear probing from a splitmix64 finaliser of (netif << 32 | ip),
+ * more slots than `capacity` so every chain ends at an empty slot, rebuilt by every sync (no
+ * tombstones); the NetIf array; and, when `routes` is not NULL, a {next_hop, netif} array indexed by
+ * route id, read through halo_route_get for ids 0, 1, ... until HALO_E_RANGE (ids are never
+ * reused). Two generations under halo_nat_sync_device's discipline: the unused one is rewritten
+ * after a device drain and published with a release store; a lookup holds the table's read lock
+ * from taking its view until its kernel is enqueued. One device per table; the caller's current
+ * device is restored. */
+HALO_API int halo_arp_sync_device(halo_arp_table_t* t, const halo_route_table_t* routes, int device);
+/* GetArpCache for n (netif, ip) pairs: d_netifs[i], or `netif` for all when d_netifs is NULL.
+ * d_verdict[i] = NONE (netif >= n_netifs), OWN_IP, MISS or HIT; d_mac8[8 * i .. + 6) = the MAC on HIT
+ * (8 bytes per entry, 8-byte aligned, zero otherwise). *d_miss_count is INCREMENTED by the MISSes.
+ * Read-only on the table (the reference does not touch ExpTime on use). Asynchronous on `stream`.
+ * HALO_E_INVAL before the first sync. n == 0 is OK. */
+HALO_API int halo_arp_lookup_device(const halo_arp_table_t* t, const uint32_t* d_ips, const uint8_t* d_netifs,
+                                    uint32_t netif, uint32_t n, uint8_t* d_mac8, uint8_t* d_verdict,
+                                    uint32_t* d_miss_count, halo_stream_t stream);
+/* The forward path's L2 step for frames (ragged layout) that NetIf `in_netif` received, given the
+ * route id FindRoute returned for each. d_select (optional): d_select[i] == 0 -> NONE (pass, for
+ * instance, the fixup result's HALO_TX_R_TTL_ALIVE bit). A selected frame shorter than 34 bytes, or
+ * whose bytes 12-13 are not 08 00, or whose route id is beyond the uploaded array (or names a NetIf
+ * >= n_netifs) -> NONE, and no byte of it is read past its length or written. Otherwise:
+ *   HALO_ROUTE_NONE -> NO_ROUTE; HALO_ROUTE_PANIC -> ROUTE_PANIC;
+ *   dst (the frame's CURRENT bytes 30-33, so the post-DNAT address) == netif[out].ip and
+ *     netif[in_netif].nat_enable == 0 -> LOOPBACK;
+ *   target = the route's next_hop when nonzero, else dst; target == netif[out].ip -> OWN_IP;
+ *   target absent -> MISS; present -> HIT: bytes 0-5 = the entry's MAC, bytes 6-11 = netif[out].mac
+ *   (exactly bytes 0-11 are written), tx_len = max(len, 60).
+ * d_results: 8-byte aligned. d_counts (optional): HALO_ARP_V_COUNT u32 counters, INCREMENTED;
+ * *d_miss_count is INCREMENTED by the MISSes. Asynchronous on `stream`. HALO_E_INVAL before the
+ * first sync and when the last sync had routes == NULL; HALO_E_RANGE: in_netif >= n_netifs. */
+HALO_API int halo_arp_encap_device(const halo_arp_table_t* t, uint8_t* d_bytes, const uint32_t* d_offsets_dw,
+                                   const uint16_t* d_lens, uint32_t n, const uint32_t* d_route_ids,
+                                   uint32_t in_netif, const uint8_t* d_select, halo_arp_result_t* d_results,
+                                   uint32_t* d_counts, uint32_t* d_miss_count, halo_stream_t stream);
+/* The ARP messages of a parsed batch: the records halo_rx_dispatch maps to HALO_RX_ACT_ARP (status
+ * OK, EtherType 0x0806, MAC_MATCH) written densely to d_msgs (8-byte aligned) in ascending frame
+ * index, with `netif` in every message. *d_count is SET to the number selected, also beyond `cap`;
+ * only the first `cap` are written. Reads bytes 6-11 and 14-41 of a selected frame and nothing of
+ * any other. d_workspace: halo_arp_gather_workspace(n) bytes, 4-byte aligned. Three launches on
+ * `stream` (tile counts, scan, scatter). */
+HALO_API uint64_t halo_arp_gather_workspace(uint32_t n);
+HALO_API int halo_arp_gather_device(const uint8_t* d_bytes, const uint32_t* d_offsets_dw, const uint16_t* d_lens,
+                                    const halo_rx_result_t* d_records, uint32_t n, uint32_t netif,
+                                    halo_arp_msg_t* d_msgs, uint32_t cap, uint32_t* d_count, void* d_workspace,
+                                    uint64_t workspace_bytes, halo_stream_t stream);
 
 /* ---- the reference engine's per-frame decision (engine/ethernet_engine.go:13-31,
  *      engine/ipv4_engine.go:18-47, engine/{udp,tcp,icmp}_engine.go) ------------------ */
