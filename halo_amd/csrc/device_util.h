@@ -88,5 +88,24 @@ __device__ __forceinline__ void load4(const uint8_t* frame, uint32_t d0, uint32_
     }
 }
 
+// load4 for a chunk the caller knows lies wholly inside the frame (d0 + 4 <= ndw): no bounds test.
+__device__ __forceinline__ void load4_inside(const uint8_t* frame, uint32_t d0, uint32_t (&w)[4]) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
+    gu32* p = (gu32*)(reinterpret_cast<const uint32_t*>(frame) + d0);
+#if HALO_RX_NT_LOADS
+    const u32x4 v = __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4*)p);
+#else
+    const u32x4 v = *(const __attribute__((address_space(1))) u32x4*)p;
+#endif
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+}
+
+// acc + lo16(w) * lo16(mult) + hi16(w) * hi16(mult): one v_dot2_u32_u16. mult 0x10001 adds both
+// halves, 0x1 / 0x10000 one of them.
+__device__ __forceinline__ uint32_t dot2_halves(uint32_t w, uint32_t mult, uint32_t acc) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, w), __builtin_bit_cast(u16x2, mult), acc, false);
+}
+
 }  // namespace
 }  // namespace halo

@@ -712,15 +712,181 @@ __device__ __forceinline__ void group_kernel_body(const RxParams& p) {
 // the 64 records in the wave's LDS (s_rec_w: 128 x 16 B) and store them fully coalesced.
 // ST: the store policy of the 64 records (store16). The default is what the ring service kernel
 // takes; the two batch kernels pass kStoreLane.
+//
+// HALO_RX_LANE_FAST: a window whose 64 frames are all plain takes straight-line code (DESIGN.md
+// §15.12). Plain: an Ethernet frame of 61..64 bytes (so each of the four round-0 chunks is one
+// 16-byte load and nothing of the frame lies beyond them), IPv4 with header byte 0x45, not a
+// fragment, UDP, and 28 <= totalLen <= L - 14 (the UDP length check of udp.go:22 included). Whether
+// the lengths qualify is one ballot before the loads, which then carry no bounds test; the header
+// tests are a second ballot once they land. Any other window, a partial last one included, takes
+// frame_finish as before. LoChan packets (LAYOUT 3) always do. 0: the code of the general path alone.
+#ifndef HALO_RX_LANE_FAST
+#define HALO_RX_LANE_FAST 1
+#endif
+#ifndef HALO_RX_LANE_FAST_MAX_WAVES
+#define HALO_RX_LANE_FAST_MAX_WAVES 65536u  // 4M frames: the largest launch measured to gain
+#endif
+template <int LAYOUT>
+constexpr bool kLaneFast = HALO_RX_LANE_FAST && !kL3<LAYOUT>;
+
+// bswap16 of a dword's low half with one v_perm_b32 (selector bytes >= 0x0C give 0x00)
+__device__ __forceinline__ uint32_t lane_total_len(const FrameState<1>& st) {
+    return __builtin_amdgcn_perm(st.buf[1][0], st.buf[1][0], 0x0C0C0001u);
+}
+
+// The header part of "plain", for a lane whose st.ndw == 16.
+__device__ __forceinline__ bool lane_plain(const FrameState<1>& st) {
+    return (st.buf[0][3] & 0x00FFFFFFu) == 0x00450008u     // ethertype 0x0800, IP byte 0 == 0x45
+        && (st.buf[1][1] & 0xFF00FFBFu) == 0x11000000u     // flags/fragment bytes 0x40|0x00, 0x00; UDP
+        && lane_total_len(st) - 28u <= st.L - 42u;         // 28 <= totalLen <= L - 14
+}
+
+// frame_store's fused tails (FUSE, there) for a record of the fast path: they read only the 32 B
+// record's fields (lo / hi: its two halves).
+template <int FUSE>
+__device__ __forceinline__ void fuse_tail(const RxParams& p, uint64_t i, const uint4& lo, const uint4& hi) {
+    if constexpr (FUSE == 1) {  // the flow key from the record's own fields (flow_key.h)
+        const uint64_t fh = flowkey::nat_hash(lo.y & 0xFFu, lo.z, lo.w, hi.x & 0xFFFFu, hi.x >> 16,
+                                              p.flow_kind, p.flow_nat);
+        p.flow_hash[i] = fh;
+        if (p.flow_bucket) p.flow_bucket[i] = (uint32_t)(fh % p.flow_buckets);  // hashmap/hashmap.go:64
+    }
+    if constexpr (FUSE == 2)  // FindRoute(dst) (route_view.h)
+        p.route_out[i] = find_route(LpmView{p.rt_tbl24, p.rt_tbl8, p.rt_lists, p.rt_ids}, lo.w);
+}
+
+// The record of a plain frame (parse_header + the segment sum + frame_store for that case), with no
+// branch: the two statuses still possible are selects in the reference's order, IP_HDR_CKSUM before
+// L4_CKSUM. Every sum is a chain of v_dot2_u32_u16 over the frame's dwords: a multiplier of 0 drops
+// a half that lies outside the region, and dword 9's (1, 2) adds the UDP length field a second time
+// for the pseudo-header. The segment [34, 14 + totalLen) ends in dwords 10..15, the only ones that
+// need a mask: dword 10 + j keeps its low clamp(sh - 32 j, 0, 32) bits, sh = 8 (totalLen - 26).
+template <int FUSE>
+__device__ __forceinline__ void lane_fast_record(const RxParams& p, uint32_t i, uint32_t lane, const FrameState<1>& st, Hist& hist,
+                                                 uint4* stage) {
+    constexpr uint32_t kLo = 0x00000001u, kHi = 0x00010000u, kBoth = 0x00010001u;
+    const uint32_t(&a)[4] = st.buf[0], (&b)[4] = st.buf[1], (&c)[4] = st.buf[2], (&d)[4] = st.buf[3];
+    const bool csum = (p.flags & HALO_RX_CSUM_ENABLE) != 0;
+    const uint32_t tl = lane_total_len(st);
+
+    // IPv4 header bytes 14..33 (ipv4.go:74-78)
+    uint32_t hs = dot2_halves(a[3], kHi, 0);
+    hs = dot2_halves(b[0], kBoth, hs);
+    hs = dot2_halves(b[1], kBoth, hs);
+    hs = dot2_halves(b[2], kBoth, hs);
+    hs = dot2_halves(b[3], kBoth, hs);
+    hs = dot2_halves(c[0], kLo, hs);
+    hs = dot2_halves(dot2_halves(hs, kBoth, 0), kBoth, 0);  // fold16
+    const bool ip_bad = csum && hs != 0xFFFFu;
+
+    // pseudo-header (src + dst, 0x0011 and the UDP length field, LE domain) + segment (udp.go:30-42)
+    uint32_t s = dot2_halves(b[2], kHi, 0);
+    s = dot2_halves(b[3], kBoth, s);
+    s = dot2_halves(c[0], kBoth, s);
+    s = dot2_halves(c[1], 0x00020001u, s);
+    const int32_t sh = (int32_t)(8u * tl) - 208;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const uint32_t w = j < 2 ? c[2 + j] : d[j - 2];
+        const int32_t x = sh - 32 * j, amt = x < 0 ? 0 : (x > 32 ? 32 : x);
+        s = dot2_halves(w & ~(uint32_t)(~0ull << amt), kBoth, s);
+    }
+    s = dot2_halves(dot2_halves(s + 0x1100u, kBoth, 0), kBoth, 0);
+    const bool l4_bad = csum && s != 0xFFFFu;
+
+    // Only constants a VALU operand can hold inline from here on (selects take no literal, and a
+    // constant in a register would live across the whole window loop).
+    const uint32_t dm_hi = a[1] & 0xFFFFu;
+    const bool mac = (a[0] == p.mac_lo && dm_hi == p.mac_hi) || (a[0] == 0xFFFFFFFFu && dm_hi == 0xFFFFu);
+    // a frame failing the header sum carries what ParseEthFrm left (parse_header's early return)
+    const uint32_t keep = ip_bad ? 0u : ~0u;
+    const uint32_t src = __builtin_amdgcn_perm(b[3], b[2], 0x02030405u);   // bytes 26..29, big-endian
+    const uint32_t dst = __builtin_amdgcn_perm(c[0], b[3], 0x02030405u);   // bytes 30..33
+    const uint32_t ports = __builtin_amdgcn_perm(c[1], c[0], 0x04050203u); // sport | dport << 16
+    const uint32_t flags_ip = ((c[0] & 0xFF00u) == 0xFF00u ? HALO_RX_F_IP_BCAST : 0u) |
+                              (dst == p.own_ip ? HALO_RX_F_DST_IS_OWN : 0u);
+    const uint32_t flags = (mac ? HALO_RX_F_MAC_MATCH : 0u) | (flags_ip & keep);
+    const uint32_t status = ip_bad ? HALO_RX_IP_HDR_CKSUM : l4_bad ? HALO_RX_L4_CKSUM : HALO_RX_OK;
+    // payload: 14, L - 14 / 34, totalLen - 20 / 42, totalLen - 28 (udp.go:47)
+    const uint32_t no_udp = l4_bad ? 8u : 0u;  // the UDP header stays in the payload
+    const uint32_t pay_off = ip_bad ? 14u : 42u - no_udp;
+    const uint32_t pay_len = ip_bad ? st.L - 14u : tl + no_udp - 28u;
+    uint4 lo, hi;
+    lo.x = status | (flags << 8) | ((uint32_t)kEthIpv4 << 16);
+    lo.y = ((ip_bad ? ~0u : (uint32_t)kIpUdp) & 0xFFu) | ((tl & keep) << 16);  // kIpUnknown == 0xFF
+    lo.z = src & keep;
+    lo.w = dst & keep;
+    hi.x = ports & keep;
+    hi.y = pay_off | (pay_len << 16);
+    hi.z = 0;
+    hi.w = 0;
+    if (p.flags & HALO_RX_RECORD_COMPACT) {  // halo_rx_record16_t
+        stage[0] = make_uint4((lo.x & 0xFFFFu) | (lo.y << 16 & 0xFF0000u), lo.z, lo.w, hi.x);
+    } else {
+        stage[0] = lo;
+        stage[1] = hi;
+    }
+    if (p.hist) {
+        // The window's OK count goes to the block's LDS counter in one add, where flush_hist puts
+        // hist.ok too: a per-lane count would be one more register live across the general path.
+        const uint64_t ok = __builtin_amdgcn_ballot_w64(status == HALO_RX_OK);
+        if (status != HALO_RX_OK) atomicAdd(&hist.s[status], 1u);
+        else if (lane == (uint32_t)__builtin_ctzll(ok)) atomicAdd(&hist.s[HALO_RX_OK], (uint32_t)__builtin_popcountll(ok));
+    }
+    fuse_tail<FUSE>(p, i, lo, hi);
+}
+
+// A wave's 64 staged records (fewer in the batch's last window) from s_rec_w to p.out.
+template <int ST>
+__device__ __forceinline__ void lane_window_store(const RxParams& p, uint32_t base, uint32_t lane, const uint4* s_rec_w) {
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t nrec = p.n - base < 64 ? p.n - base : 64;  // records of this wave
+    if (p.flags & HALO_RX_RECORD_COMPACT) {
+        if (lane < nrec) store16<ST>(reinterpret_cast<uint4*>(p.out) + base + lane, s_rec_w[lane]);
+    } else {
+        uint4* out4 = reinterpret_cast<uint4*>(p.out) + 2ull * base;
+        if (lane < 2 * nrec) store16<ST>(out4 + lane, s_rec_w[lane]);
+        if (64 + lane < 2 * nrec) store16<ST>(out4 + 64 + lane, s_rec_w[64 + lane]);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// The whole window on the fast path, after frame_meta: false (nothing stored, st.buf not to be
+// used) when some frame of it is not plain.
+template <int FUSE, int ST>
+__device__ __forceinline__ bool lane_window_fast(const RxParams& p, uint32_t base, uint32_t lane, FrameState<1>& st,
+                                                uint4* s_rec_w, Hist& hist) {
+    if (__builtin_amdgcn_ballot_w64(st.ndw != 16u) != 0) return false;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) load4_inside(st.frame, u * 4, st.buf[u]);
+    // The header tests read chunks 0 and 1 only; this use keeps the compiler from moving the last
+    // chunk's load below the branch, where it would be a second memory round trip.
+    asm volatile("" ::"v"(st.buf[3][3]));
+    if (__builtin_amdgcn_ballot_w64(!lane_plain(st)) != 0) return false;
+    const bool compact = (p.flags & HALO_RX_RECORD_COMPACT) != 0;
+    lane_fast_record<FUSE>(p, base + lane, lane, st, hist, &s_rec_w[compact ? lane : 2 * lane]);
+    lane_window_store<ST>(p, base, lane, s_rec_w);
+    return true;
+}
+
 template <int LAYOUT, int FUSE, int ST = kStoreDefault>
 __device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t base, uint32_t lane, FrameState<1>& st,
                                                    uint4* s_rec_w, Hist& hist);
 template <int LAYOUT, int FUSE, int ST = kStoreDefault>
 __device__ __forceinline__ void lane_window(const RxParams& p, uint32_t base, uint32_t lane, uint4* s_rec_w,
-                                           Hist& hist) {
+                                           Hist& hist, bool try_fast = true) {
     const uint32_t i = base + lane;
     FrameState<1> st;
     frame_meta<LAYOUT>(p, i, i < p.n, st);
+    if (kLaneFast<LAYOUT> && try_fast) {  // (try_fast is a constant when the knob is off)
+        // The outcome passes through an empty asm so that the compiler cannot thread the fast
+        // attempt's two exits into the general path's entry: as one if / else the blocks are laid out
+        // general first, the attempt's loads stay live across all of it, and the kernel needs 87
+        // VGPRs instead of 72.
+        uint32_t done = __builtin_amdgcn_readfirstlane(lane_window_fast<FUSE, ST>(p, base, lane, st, s_rec_w, hist));
+        asm volatile("" : "+s"(done));
+        if (done == 1) return;
+    }
     frame_loads<1>(0, st);
     lane_window_finish<LAYOUT, FUSE, ST>(p, base, lane, st, s_rec_w, hist);
 }
@@ -761,16 +927,7 @@ __device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t b
     const uint32_t i = base + lane;
     frame_finish<1, FUSE, HALO_RX_LANE_LATER, kRound0<1>, kL3<LAYOUT>>(p, i, i < p.n, 0, lane, st, hist,
                                                                      &s_rec_w[compact ? lane : 2 * lane]);
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t nrec = p.n - base < 64 ? p.n - base : 64;  // records of this wave
-    if (compact) {
-        if (lane < nrec) store16<ST>(reinterpret_cast<uint4*>(p.out) + base + lane, s_rec_w[lane]);
-    } else {
-        uint4* out4 = reinterpret_cast<uint4*>(p.out) + 2ull * base;
-        if (lane < 2 * nrec) store16<ST>(out4 + lane, s_rec_w[lane]);
-        if (64 + lane < 2 * nrec) store16<ST>(out4 + 64 + lane, s_rec_w[64 + lane]);
-    }
-    __builtin_amdgcn_wave_barrier();
+    lane_window_store<ST>(p, base, lane, s_rec_w);
 }
 
 template <int LAYOUT, int FUSE>
@@ -808,7 +965,14 @@ rx_lane_kernel(const RxParams p) {
         frame_meta<LAYOUT>(p, i + nwaves * 64, i + nwaves * 64 < p.n, nx);
         lane_window_finish<LAYOUT, FUSE, kStoreLane>(p, base, lane, st, s_rec[w], hist);
 #else
+        // A 16M-frame launch is bound by memory and ran 2 % slower with the fast path (waves that
+        // finish sooner put more requests in flight), 4M 3 % and 1M 14 % faster:
+        // launches of up to HALO_RX_LANE_FAST_MAX_WAVES waves only.
+#if HALO_RX_LANE_FAST
+        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= HALO_RX_LANE_FAST_MAX_WAVES);
+#else
         lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist);
+#endif
 #endif
     }
     flush_hist(p, hist);
@@ -855,7 +1019,11 @@ __global__ void __launch_bounds__(HALO_RX_LANE_BLOCK) rx_lane_multi_kernel(const
         p.out = mp.out[b];
         p.n = mp.n[b];
         const uint32_t base = (win - (b ? mp.win_end[b - 1] : 0u)) * 64u;
+#if HALO_RX_LANE_FAST
+        lane_window<LAYOUT, 0, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= HALO_RX_LANE_FAST_MAX_WAVES);
+#else
         lane_window<LAYOUT, 0, kStoreLane>(p, base, lane, s_rec[w], hist);
+#endif
     }
     flush_hist(mp.p, hist);
 }
