@@ -4,6 +4,9 @@ path and the general one can go wrong: whole and partial windows, one deviating 
 or 63 of an otherwise plain window, failing checksums inside a fast window, every frame and segment
 length the predicate admits, and the other entry points that share the window code. Every case
 compares every record byte and the status histogram; nothing depends on which path a window took.
+The deviating-frame and failing-checksum cases run a second time without a histogram, which changes
+how many windows a wave of a small grid takes. test_gpu_lane_fastpath_sweep.py and
+test_gpu_resident_fastpath.py build on the helpers here.
 """
 from __future__ import annotations
 
@@ -68,25 +71,39 @@ def to_dev(dev, data, offs, lens):
             torch.from_numpy(lens.view(np.int16)).to(dev))
 
 
-def check(dev, oracle_lib, frames, flags, compact, what):
-    """The frames through the lane kernel (variant 1) with a histogram; records (32 B, or 16 B with
-    `compact`) and counts == the oracle's. Returns the oracle's records."""
+def pack_rows(rows: np.ndarray, lens: np.ndarray, lead_dw: int = 1, gaps: bool = True):
+    """pack() for frames held as the rows of a uint8 array (row i: lens[i] bytes, the rest of the row
+    ignored), without a Python loop per frame: the sweeps lay out 256k frames."""
+    n = len(lens)
+    size = ((lens.astype(np.int64) + 3) & ~3) + (4 * (np.arange(n) % 3) if gaps else 0)
+    start = 4 * lead_dw + np.concatenate([[0], np.cumsum(size)[:-1]])
+    data = np.full(4 * lead_dw + int(size.sum()) + 64, 0x5A, np.uint8)
+    col = np.arange(rows.shape[1])
+    inside = col[None, :] < lens[:, None]
+    data[(start[:, None] + col[None, :])[inside]] = rows[inside]
+    return data, (start // 4).astype(np.uint32), lens.astype(np.uint16)
+
+
+def check_packed(dev, devbufs, oracle_ref, flags, compact, what, with_hist=True):
+    """A packed batch already on the device (devbufs: to_dev's three tensors) through the lane kernel
+    (variant 1), with a histogram or without one (hist = NULL: launch_variant then gives each wave of
+    a small grid one window, not two); records (32 B, or 16 B with `compact`) and counts == the
+    oracle's (oracle_ref: what rx_batch returned for these frames and flags)."""
     import torch
 
     from halo_amd import _lib
     from halo_amd._lib import NetIf, compact_of
 
-    data, offs, lens = pack(frames)
-    n = len(frames)
-    want, whist = oracle_lib.rx_batch(data, lens, oracle_lib.NetIf.make(), flags, offsets_dw=offs)
-    d, o, ln = to_dev(dev, data, offs, lens)
+    d, o, ln = devbufs
+    want, whist = oracle_ref
+    n = len(want)
     width = 16 if compact else 32
     out = torch.full((n, width), 0xEE, dtype=torch.uint8, device=dev)
     hist = torch.zeros(14, dtype=torch.int32, device=dev)
     word = flags | _lib.variant_flags(1) | (_lib.HALO_RX_RECORD_COMPACT if compact else 0)
     _lib.check("parse", _lib.lib.halo_rx_parse_batch_device(
-        d.data_ptr(), o.data_ptr(), ln.data_ptr(), n, word, NetIf.make(), int(lens.max()), out.data_ptr(),
-        hist.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        d.data_ptr(), o.data_ptr(), ln.data_ptr(), n, word, NetIf.make(), int(ln.max()), out.data_ptr(),
+        hist.data_ptr() if with_hist else None, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     got = out.cpu().numpy()
     if compact:
@@ -95,8 +112,19 @@ def check(dev, oracle_lib, frames, flags, compact, what):
         assert bad.size == 0, (what, "compact records differ", bad[:8].tolist())
     else:
         assert_records_equal(got.reshape(-1).view(_lib.RESULT_DTYPE), want, None, what)
-    assert np.array_equal(hist.cpu().numpy().astype(np.int64), whist.astype(np.int64)), (what, "histogram")
-    return want
+    if with_hist:
+        assert np.array_equal(hist.cpu().numpy().astype(np.int64), whist.astype(np.int64)), (what, "histogram")
+    else:
+        assert not hist.any(), (what, "a histogram nobody passed was written")
+
+
+def check(dev, oracle_lib, frames, flags, compact, what, with_hist=True):
+    """The frames through the lane kernel (variant 1), with a histogram unless `with_hist` is False;
+    records (32 B, or 16 B with `compact`) and counts == the oracle's. Returns the oracle's records."""
+    data, offs, lens = pack(frames)
+    ref = oracle_lib.rx_batch(data, lens, oracle_lib.NetIf.make(), flags, offsets_dw=offs)
+    check_packed(dev, to_dev(dev, data, offs, lens), ref, flags, compact, what, with_hist)
+    return ref[0]
 
 
 def golden_frame(golden, name: str) -> bytes:
@@ -137,36 +165,56 @@ def test_all_plain_windows(dev, oracle_lib, mode):
         assert np.all(want["status"] == 0) and np.all(want["payload_len"] == 22)
 
 
-@pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
-def test_one_deviating_frame(dev, oracle_lib, golden, mode):
-    """n = 128: window 0 plain but for one frame at lane 0, 31 or 63; window 1 all plain."""
+def _one_deviating_frame(dev, oracle_lib, golden, mode, with_hist):
     flags, compact = mode
     base = [plain(k) for k in range(128)]
-    clean = check(dev, oracle_lib, base, flags, compact, "128 plain")
+    clean = check(dev, oracle_lib, base, flags, compact, "128 plain", with_hist)
     for name, frame in deviants(golden):
         for lane in (0, 31, 63):
             frames = list(base)
             frames[lane] = frame
-            want = check(dev, oracle_lib, frames, flags, compact, f"{name} at lane {lane}")
+            want = check(dev, oracle_lib, frames, flags, compact, f"{name} at lane {lane}", with_hist)
             assert want[64:].tobytes() == clean[64:].tobytes(), (name, lane, "window 1 changed")
+
+
+@pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
+def test_one_deviating_frame(dev, oracle_lib, golden, mode):
+    """n = 128: window 0 plain but for one frame at lane 0, 31 or 63; window 1 all plain."""
+    _one_deviating_frame(dev, oracle_lib, golden, mode, True)
+
+
+@pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
+def test_one_deviating_frame_without_histogram(dev, oracle_lib, golden, mode):
+    """The same with hist = NULL, the benchmark's launch: the grid is not halved, so the two windows
+    go to two waves."""
+    _one_deviating_frame(dev, oracle_lib, golden, mode, False)
+
+
+def _failing_checksums(dev, oracle_lib, mode, with_hist):
+    flags, compact = mode
+    frames = [plain(k) for k in range(64)]
+    clean = check(dev, oracle_lib, frames, flags, compact, "64 plain", with_hist)
+    frames[5] = flip(frames[5], 22, 3)
+    frames[40] = flip(frames[40], 50, 6)
+    frames[41] = flip(flip(frames[41], 22, 3), 50, 6)
+    want = check(dev, oracle_lib, frames, flags, compact, "failing checksums", with_hist)
+    if flags & 1:
+        assert [int(want["status"][i]) for i in (5, 40, 41)] == [IP_HDR_CKSUM, L4_CKSUM, IP_HDR_CKSUM]
+    keep = np.ones(64, bool)
+    keep[[5, 40, 41]] = False
+    assert want[keep].tobytes() == clean[keep].tobytes()
 
 
 @pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
 def test_failing_checksums_inside_a_fast_window(dev, oracle_lib, mode):
     """One bit flipped in the IPv4 header of frame 5 (TTL), one in the UDP payload of frame 40, both
     in frame 41: every frame still plain by the predicate; the first failing check wins."""
-    flags, compact = mode
-    frames = [plain(k) for k in range(64)]
-    clean = check(dev, oracle_lib, frames, flags, compact, "64 plain")
-    frames[5] = flip(frames[5], 22, 3)
-    frames[40] = flip(frames[40], 50, 6)
-    frames[41] = flip(flip(frames[41], 22, 3), 50, 6)
-    want = check(dev, oracle_lib, frames, flags, compact, "failing checksums")
-    if flags & 1:
-        assert [int(want["status"][i]) for i in (5, 40, 41)] == [IP_HDR_CKSUM, L4_CKSUM, IP_HDR_CKSUM]
-    keep = np.ones(64, bool)
-    keep[[5, 40, 41]] = False
-    assert want[keep].tobytes() == clean[keep].tobytes()
+    _failing_checksums(dev, oracle_lib, mode, True)
+
+
+@pytest.mark.parametrize("mode", MODES, ids=MODE_IDS)
+def test_failing_checksums_inside_a_fast_window_without_histogram(dev, oracle_lib, mode):
+    _failing_checksums(dev, oracle_lib, mode, False)
 
 
 def test_mac_and_address_flags(dev, oracle_lib):
