@@ -160,3 +160,17 @@ def assert_build_equal(frames, lens, res, ip_end, run, expect, what="", names=No
             raise AssertionError(f"{what}: frame {i} differs first at byte {k}: got {got[k:k+8].hex()} "
                                  f"want {want[k:k+8].hex()}")
     assert ip_end == run["ip_id_end"], (what, ip_end, run["ip_id_end"])
+
+
+def random_tx_ops(n, seed):
+    """n halo_tx_op_t with random step sets, addresses and ports."""
+    from halo_amd import protocol
+
+    rng = np.random.default_rng(seed)
+    ops = protocol.tx_ops(n)
+    ops["steps"] = rng.integers(0, 32, n, dtype=np.uint8)
+    ops["dst_ip"] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    ops["src_ip"] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    ops["dst_port"] = rng.integers(0, 1 << 16, n, dtype=np.uint32).astype(np.uint16)
+    ops["src_port"] = rng.integers(0, 1 << 16, n, dtype=np.uint32).astype(np.uint16)
+    return ops

@@ -211,3 +211,55 @@ def fill(table, model, tuples, now):
         assert (got is None) == (want is None)
         if want is not None:
             assert flow_tuple(got) == flow_tuple(want)
+
+
+# ---- the record and op builders of the device tests ------------------------------------------------
+REMOTE = 0x08080000
+TX_TTL = 0x02
+
+
+def records(m: NatModel, direction, n, seed):
+    """n records for `direction`: about half hit a flow of the model (ICMP ones with a remote port
+    the key ignores), the rest are misses, port-mapping hits and unparsed (0xFF) records."""
+    from halo_amd._lib import RESULT_DTYPE
+
+    rng = np.random.RandomState(seed)
+    flows = m.list()
+    r = np.zeros(n, RESULT_DTYPE)
+    r["l4_seq"] = rng.randint(0, 1 << 31, n)  # fields no lookup reads
+    for i in range(n):
+        kind = rng.randint(0, 10)
+        if kind < 5 and flows:
+            f = flows[rng.randint(0, len(flows))]
+            rip = f["remote_ip"] or (REMOTE | rng.randint(1, 1 << 16))
+            rport = f["remote_port"] or rng.randint(1, 65536)
+            if direction == WAN:
+                rec = (f["proto"], rip, rport, f["wan_ip"], f["wan_port"])
+            else:
+                rec = (f["proto"], f["lan_ip"], f["lan_port"], rip, rport)
+        elif kind < 7:  # a miss: a random tuple
+            rec = (int(rng.choice([1, 6, 17])), REMOTE | rng.randint(1, 1 << 16), rng.randint(1, 65536),
+                   WAN_IP if direction == WAN else 0xC0A80000 | rng.randint(2, 250), rng.randint(1, 65536))
+        elif kind < 9 and m.maps:  # a port mapping (or, for ICMP, not)
+            wp, lip, lp, pr = m.maps[rng.randint(0, len(m.maps))]
+            pr = pr if rng.randint(0, 4) else 1
+            rec = (pr, REMOTE | 7, 999, WAN_IP, wp) if direction == WAN else (pr, lip, lp, REMOTE | 7, 999)
+        else:
+            rec = (0xFF, 0, 0, 0, 0)
+        r["ip_proto"][i], r["src_ip"][i], r["sport"][i], r["dst_ip"][i], r["dport"][i] = rec
+    return r
+
+
+def ops(n, seed):
+    """Ops as a caller chaining lookups leaves them: HALO_TX_TTL set, sentinels everywhere else."""
+    from halo_amd._lib import TX_OP_DTYPE
+
+    rng = np.random.RandomState(seed)
+    out = np.zeros(n, TX_OP_DTYPE)
+    out["steps"] = TX_TTL
+    for f in ("dst_ip", "src_ip"):
+        out[f] = rng.randint(0, 1 << 31, n)
+    for f in ("dst_port", "src_port", "pad2"):
+        out[f] = rng.randint(0, 1 << 16, n)
+    out["pad"] = 0xA5
+    return out

@@ -262,6 +262,117 @@ def differential(make, calls, max_n, seed, pool_size=300, capacity=128, slots_lo
     s.close()
 
 
+# ---- past one grid and one scan pass (tests/scale_cases.py has the boundaries) --------------------
+def numpy_frames(dst_ids, src_ids, lens=None, ethertypes=None, src_mcast=None, dst_bcast=None):
+    """Frames between the MACs M.mac(id), built without a Python loop per byte: (frames as a list
+    of bytes for the model, packed = (bytes, offsets_dw, lens) for the switch). Frames lie back to
+    back at dword boundaries; a frame shorter than its header is cut like M.frame's."""
+    n = len(dst_ids)
+    lens = np.full(n, 64, np.uint16) if lens is None else np.asarray(lens, np.uint16)
+    hdr = np.zeros((n, 14), np.uint8)
+    for ids, base in ((np.asarray(dst_ids, np.uint32), 0), (np.asarray(src_ids, np.uint32), 6)):
+        hdr[:, base], hdr[:, base + 1] = 0x02, 0x10
+        for b in range(4):
+            hdr[:, base + 2 + b] = (ids >> (8 * (3 - b))) & 0xFF
+    if dst_bcast is not None:
+        hdr[dst_bcast, 0:6] = 0xFF
+    if src_mcast is not None:
+        hdr[src_mcast, 6:12] = np.frombuffer(MCAST_SRC, np.uint8)
+    et = np.full(n, 0x0800, np.uint16) if ethertypes is None else np.asarray(ethertypes, np.uint16)
+    hdr[:, 12], hdr[:, 13] = et >> 8, et & 0xFF
+    size = (lens.astype(np.int64) + 3) & ~3
+    offs = np.zeros(n, np.int64)
+    offs[1:] = np.cumsum(size)[:-1]
+    data = np.zeros(int(size.sum()) + 16, np.uint8)
+    col = np.arange(14)
+    keep = col[None, :] < lens[:, None]
+    data[(offs[:, None] + col[None, :])[keep]] = hdr[keep]
+    frames = [data[o:o + ln].tobytes() for o, ln in zip(offs.tolist(), lens.tolist())]
+    return frames, (data, (offs // 4).astype(np.uint32), lens)
+
+
+def numpy_random_frames(rng, pool_size, n, p_bad=0.08):
+    """random_frames, vectorised: the same drop classes in the same shares between MACs
+    M.mac(0 .. pool_size - 1); lengths 42 / 60 / 64 / 128 and, one frame in 512, 1514."""
+    src, dst = rng.integers(0, pool_size, n), rng.integers(0, pool_size, n)
+    kind = rng.random(n)
+    lens = rng.choice(np.array([42, 60, 64, 128], np.uint16), n)
+    lens[rng.integers(0, 512, n) == 0] = 1514
+    bad_len = kind < p_bad / 4
+    lens[bad_len] = rng.choice(np.array([0, 13, 41, 1515, 2000], np.uint16), int(bad_len.sum()))
+    et = np.full(n, 0x0800, np.uint16)
+    bad_et = (kind >= p_bad / 4) & (kind < p_bad / 2)
+    et[bad_et] = rng.choice(np.array([0x8100, 0x0000, 0x0801], np.uint16), int(bad_et.sum()))
+    return numpy_frames(dst, src, lens, et, src_mcast=(kind >= p_bad / 2) & (kind < 3 * p_bad / 4),
+                        dst_bcast=(kind >= 3 * p_bad / 4) & (kind < p_bad))
+
+
+def scale_new_macs(make):
+    """Every frame a broadcast from a new source, one scan pass plus 300 frames; the capacity ends
+    admission inside tile 1,025, the first tile of the scan's second pass: its rank is the carry."""
+    from tests import scale_cases as S
+
+    n = S.past("sw_scan_pass", 300)
+    tile, width = S.BOUNDARIES["sw_scan_pass"]["first_past"] - 1, 256
+    cap = tile + 100
+    assert tile % width == 0 and tile // width == 1024 and cap < n
+    s = make(vlans=[1, 1], capacity=cap, max_batch=n)
+    ids = np.arange(n, dtype=np.uint32)
+    frames, packed = numpy_frames(ids, ids, dst_bcast=np.ones(n, bool))
+    (v, _, _), = s.forward_many([(0, frames, 1, packed)])
+    assert np.array_equal(v, np.r_[np.full(cap, M.FLOOD, np.uint8), np.full(n - cap, M.TABLE_FULL, np.uint8)])
+    s.close()
+
+
+def scale_differential(make):
+    """Random sources and destinations over a pool larger than the capacity, past the resolve
+    kernel's grid: irregular per-tile counts of new MACs through the scan's carry, room running out
+    beyond tile 1,024, held MACs another port taught, and every counter over two trips."""
+    from tests import scale_cases as S
+
+    n, pool, cap = S.past("sw_resolve_trip", 257), 400_000, 250_000
+    rng = np.random.default_rng(17)
+    s = make(vlans=[1, 1, 2], capacity=cap, max_batch=n)
+    f0, p0 = numpy_random_frames(rng, 3_000, 2_000)
+    frames, packed = numpy_random_frames(rng, pool, n)
+    s.forward_many([(1, f0, 40, p0)])
+    held = len(s.model.table)
+    (v, p, _), = s.forward_many([(0, frames, 77, packed)])
+    full = np.flatnonzero(v == M.TABLE_FULL)
+    pass_frames = S.BOUNDARIES["sw_scan_pass"]["first_past"] - 1
+    assert held > 500 and len(s.model.table) == cap and full.size and full[0] > pass_frames
+    assert (p[v == M.UNICAST] == 1).any() and (p[v == M.UNICAST] == 0).any()
+    assert (np.bincount(v, minlength=6) > 0).all()  # every verdict, so every counter, occurred
+    s.close()
+
+
+def scale_rebuild(make):
+    """A table of 2^20 slots: two calls at different times fill it, an expiry tick removes the first
+    call's half through the rebuild kernel's second trip, and one call addressed to every MAC
+    unicasts to the survivors and floods the rest."""
+    from tests import scale_cases as S
+
+    cap, half = 300_000, 150_000
+    s = make(vlans=[1, 1, 1], capacity=cap, max_batch=cap)
+    slots = int(s.sw.layout_stats()["slots"])
+    assert slots == 1 << 20 and slots >= S.BOUNDARIES["sw_rebuild_trip"]["first_past"]
+    # an odd multiplier mod 2^32: distinct ids spread over the hash's input
+    ids = (np.arange(cap, dtype=np.uint64) * 2654435761 & 0xFFFFFFFF).astype(np.uint32)
+    for k, now in ((0, 1000), (1, 1200)):
+        part = ids[k * half:(k + 1) * half]
+        frames, packed = numpy_frames(part, part, dst_bcast=np.ones(half, bool))
+        s.forward_many([(k, frames, now, packed)])
+    assert len(s.model.table) == cap
+    assert s.expire(1400) == half
+    frames, packed = numpy_frames(ids, np.full(cap, ids[-1], np.uint32))
+    (v, p, _), = s.forward_many([(2, frames, 1401, packed)])
+    assert np.all(v[:half] == M.FLOOD) and np.all(v[half:] == M.UNICAST)
+    assert np.all(p[half:-1] == 1) and p[-1] == 2  # the last MAC is the sender: it moved to port 2
+    s.close()
+
+
+SCALE_CASES = {"new_macs": scale_new_macs, "differential": scale_differential, "rebuild": scale_rebuild}
+
 CASES = {"in_batch_order": case_in_batch_order, "no_learning_on_drops": case_no_learning_on_drops,
          "capacity": case_capacity, "expiry": case_expiry, "length_edges": case_length_edges, "long_lengths": case_long_lengths,
          "every_verdict": every_verdict}

@@ -15,7 +15,9 @@ from tests import arp_model as M
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1000]
-NH_HIT, NH_MISS, NH_OWN, PANIC, ECMP, BAD_NETIF = 0xAC100000, 0xAC110000, 0xAC120000, 0xAC140000, 0xAC150000, 0xAC160000
+NH_HIT, NH_MISS, NH_OWN, PANIC, ECMP, BAD_NETIF = K.NH_HIT, K.NH_MISS, K.NH_OWN, K.PANIC, K.ECMP, K.BAD_NETIF
+# the batch builders are shared with tests/test_gpu_scale.py
+_absent, _ipv4_frame, _pack, _mixed_batch, _route_of = K.absent, K.ipv4_frame, K.pack, K.mixed_batch, K.route_of
 
 
 @pytest.fixture(scope="module")
@@ -29,34 +31,12 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _absent(keys, nif, k):
-    """The k-th address of NetIf nif's /24 that is neither a key nor the own address."""
-    base = K.NETIFS[nif].ip & 0xFFFFFF00
-    free = [base | h for h in range(2, 255) if (nif, base | h) not in keys]
-    return free[k % len(free)]
-
-
 @pytest.fixture(scope="module")
 def world(dev):
     """The forced table, synced with a real route table that has direct routes, next-hop routes, an
     emptied list and an ECMP list."""
-    from halo_amd.route import RouteTable
-
     pair, keys = K.forced_table(lambda **kw: K.Pair(**kw))
-    rt = RouteTable(0)
-    E = RouteTable.entry
-    for nif, m in enumerate(K.NETIFS):
-        rt.AddRoute(E(m.ip & 0xFFFFFF00, 0xFFFFFF00, 0, nif))
-    hit_nif, hit_ip = keys[0]
-    rt.AddRoute(E(NH_HIT, 0xFFFF0000, hit_ip, hit_nif))
-    rt.AddRoute(E(NH_MISS, 0xFFFF0000, _absent(keys, 2, 0), 2))
-    rt.AddRoute(E(NH_OWN, 0xFFFF0000, K.NETIFS[1].ip, 1))
-    gone = E(PANIC, 0xFFFF0000, keys[1][1], keys[1][0])
-    rt.AddRoute(gone)
-    rt.DeleteRoute(gone)  # the emptied list still ends a lookup
-    rt.AddRoute(E(ECMP, 0xFFFF0000, keys[2][1], keys[2][0]))
-    rt.AddRoute(E(ECMP, 0xFFFF0000, _absent(keys, 0, 1), 0))
-    rt.AddRoute(E(BAD_NETIF, 0xFFFF0000, 0, 9))  # a NetIf the ARP table does not have
+    rt = K.world_routes(keys)
     rt.sync()
     pair.t.sync(rt)
     assert not pair.t.dirty
@@ -65,93 +45,11 @@ def world(dev):
     rt.close()
 
 
-def _route_of(rt, rid):
-    if rid in (M.ROUTE_NONE, M.ROUTE_PANIC_ID):
-        return rid
-    try:
-        r = rt.get(rid)[0]
-    except Exception:
-        return None
-    return int(r["next_hop"]), int(r["netif"])
-
-
-def _ipv4_frame(rng, length, dst_ip, ethertype=0x0800):
-    """`length` bytes: a MAC header that is not ours to judge, an EtherType, random bytes, and the
-    destination address at bytes 30-33 when the frame has them."""
-    f = bytearray(rng.integers(0, 256, length, dtype=np.uint8).tobytes())
-    if length >= 14:
-        f[12:14] = bytes([ethertype >> 8, ethertype & 255])
-    if length >= 34:
-        f[30:34] = M.ip_bytes(dst_ip)
-    return bytes(f)
-
-
-def _pack(rng, frames):
-    """Frames at 4-byte boundaries with random extra 4-byte gaps and garbage between them."""
-    offs, pos = [], 0
-    for f in frames:
-        pos += 4 * int(rng.integers(0, 3))
-        offs.append(pos)
-        pos += (len(f) + 3) & ~3
-    data = rng.integers(0, 256, pos + 16, dtype=np.uint8)
-    for o, f in zip(offs, frames):
-        data[o:o + len(f)] = np.frombuffer(f, np.uint8)
-    return data, (np.array(offs, np.int64) // 4).astype(np.uint32), np.array([len(f) for f in frames], np.uint16)
-
-
 def _up(dev, data, offs, lens):
     import torch
 
     return (torch.from_numpy(data).to(dev), torch.from_numpy(offs.view(np.int32)).to(dev),
             torch.from_numpy(lens.view(np.int16)).to(dev))
-
-
-def _mixed_batch(rng, keys, n):
-    """n frames cycling through every case of the L2 step: (frames, intended dst per frame, select,
-    forced route id or None, case name)."""
-    lens_pool = [34, 60, 61, 62, 63, 64, 100, 1514]
-    frames, dsts, select, forced, names = [], [], [], [], []
-    kinds = ["hit_direct", "unselected", "short33", "len34_hit", "not_ipv4", "bad_route_id", "no_route", "panic", "own_dst",
-             "own_next_hop", "miss_direct", "miss_next_hop", "hit_next_hop", "ecmp", "bad_netif", "hit_direct"]
-    for i in range(n):
-        kind = kinds[i % len(kinds)] if n > 1 else "hit_direct"
-        nif, ip = keys[(i // len(kinds) + i) % len(keys)]
-        length, et, sel, frc = lens_pool[i % len(lens_pool)], 0x0800, 1, None
-        dst = ip
-        if kind == "unselected":
-            sel = 0
-        elif kind == "short33":
-            length = 33
-        elif kind == "len34_hit":
-            length = 34
-        elif kind == "not_ipv4":
-            et = [0x0806, 0x86DD, 0x0801, 0x0900][i % 4]
-        elif kind == "bad_route_id":
-            frc = 1000 + i
-        elif kind == "no_route":
-            dst = 0x08080808
-        elif kind == "panic":
-            dst = PANIC | 7
-        elif kind == "own_dst":
-            dst = K.NETIFS[i % 3].ip
-        elif kind == "own_next_hop":
-            dst = NH_OWN | (i & 0xFFFF)
-        elif kind == "miss_direct":
-            dst = _absent(keys, i % 3, i)
-        elif kind == "miss_next_hop":
-            dst = NH_MISS | (i & 0xFFFF)
-        elif kind == "hit_next_hop":
-            dst = NH_HIT | (i & 0xFFFF)
-        elif kind == "ecmp":
-            dst = ECMP | ((i * 7919) & 0xFFFF)
-        elif kind == "bad_netif":
-            dst = BAD_NETIF | 5
-        frames.append(_ipv4_frame(rng, length, dst, et))
-        dsts.append(dst)
-        select.append(sel)
-        forced.append(frc)
-        names.append(kind)
-    return frames, np.array(dsts, np.uint32), np.array(select, np.uint8), forced, names
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -216,22 +114,7 @@ def test_lookup_matches_model(dev, world, n):
 
     pair, keys, _ = world
     rng = np.random.default_rng(900 + n)
-    nifs = np.zeros(n, np.uint8)
-    ips = np.zeros(n, np.uint32)
-    for i in range(n):
-        kind = i % 5
-        nif, ip = keys[i % len(keys)]  # every entry: the end of the longest chain and the wrapped ones among them
-        if kind == 1:  # absent: with one empty slot in sixteen its probe runs to the end of a chain
-            nif = i % 3
-            ip = _absent(keys, nif, i)
-        elif kind == 2 and i % 2:
-            nif = i % 3
-            ip = K.NETIFS[nif].ip
-        elif kind == 3 and i % 3 == 0:
-            nif = [3, 64, 255][(i // 15) % 3]  # a NetIf the table does not have
-        elif kind == 4:
-            ip = int(rng.integers(0, 1 << 32))
-        nifs[i], ips[i] = nif, ip
+    nifs, ips = K.lookup_mix(rng, keys, n)
     d_ips = torch.from_numpy(ips.view(np.int32)).to(dev)
     d_nifs = torch.from_numpy(nifs).to(dev)
     for uniform in (None, 0, 2, 3):

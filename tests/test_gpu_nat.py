@@ -13,8 +13,9 @@ from tests import nat_model as M
 
 pytestmark = pytest.mark.gpu
 
-REMOTE = 0x08080000
-TX_TTL, TX_RECALC = 0x02, 0x08
+REMOTE = M.REMOTE
+TX_TTL, TX_RECALC = M.TX_TTL, 0x08
+_records, _ops = M.records, M.ops  # shared with tests/test_gpu_scale.py
 
 
 @pytest.fixture(scope="module")
@@ -55,53 +56,6 @@ def tables(dev):
         "forced_cone": _pair(M.FULL_CONE, M.random_tuples(fc, M.FIXTURE_FLOWS), M.FIXTURE_LOG2),
         "5000": _pair(M.SYMMETRIC, M.random_tuples(9, 5000), 0, MAPPINGS),
     }
-
-
-def _records(m: M.NatModel, direction, n, seed):
-    """n records for `direction`: about half hit a flow of the model (ICMP ones with a remote port
-    the key ignores), the rest are misses, port-mapping hits and unparsed (0xFF) records."""
-    from halo_amd._lib import RESULT_DTYPE
-
-    rng = np.random.RandomState(seed)
-    flows = m.list()
-    r = np.zeros(n, RESULT_DTYPE)
-    r["l4_seq"] = rng.randint(0, 1 << 31, n)  # fields no lookup reads
-    for i in range(n):
-        kind = rng.randint(0, 10)
-        if kind < 5 and flows:
-            f = flows[rng.randint(0, len(flows))]
-            rip = f["remote_ip"] or (REMOTE | rng.randint(1, 1 << 16))
-            rport = f["remote_port"] or rng.randint(1, 65536)
-            if direction == M.WAN:
-                rec = (f["proto"], rip, rport, f["wan_ip"], f["wan_port"])
-            else:
-                rec = (f["proto"], f["lan_ip"], f["lan_port"], rip, rport)
-        elif kind < 7:  # a miss: a random tuple
-            rec = (int(rng.choice([1, 6, 17])), REMOTE | rng.randint(1, 1 << 16), rng.randint(1, 65536),
-                   M.WAN_IP if direction == M.WAN else 0xC0A80000 | rng.randint(2, 250), rng.randint(1, 65536))
-        elif kind < 9 and m.maps:  # a port mapping (or, for ICMP, not)
-            wp, lip, lp, pr = m.maps[rng.randint(0, len(m.maps))]
-            pr = pr if rng.randint(0, 4) else 1
-            rec = (pr, REMOTE | 7, 999, M.WAN_IP, wp) if direction == M.WAN else (pr, lip, lp, REMOTE | 7, 999)
-        else:
-            rec = (0xFF, 0, 0, 0, 0)
-        r["ip_proto"][i], r["src_ip"][i], r["sport"][i], r["dst_ip"][i], r["dport"][i] = rec
-    return r
-
-
-def _ops(n, seed):
-    """Ops as a caller chaining lookups leaves them: HALO_TX_TTL set, sentinels everywhere else."""
-    from halo_amd._lib import TX_OP_DTYPE
-
-    rng = np.random.RandomState(seed)
-    ops = np.zeros(n, TX_OP_DTYPE)
-    ops["steps"] = TX_TTL
-    for f in ("dst_ip", "src_ip"):
-        ops[f] = rng.randint(0, 1 << 31, n)
-    for f in ("dst_port", "src_port", "pad2"):
-        ops[f] = rng.randint(0, 1 << 16, n)
-    ops["pad"] = 0xA5
-    return ops
 
 
 def _launch(dev, t, direction, recs, now, ops, skip=None, compact=False, stream=None):

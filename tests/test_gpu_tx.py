@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import assert_tx_equal, tx_batch_arrays, tx_golden
+from tests.helpers import random_tx_ops as _random_ops  # shared with tests/test_gpu_scale.py
 
 pytestmark = pytest.mark.gpu
 
@@ -87,19 +88,6 @@ def test_tx_empty_batch_and_validation(dev):
                                         None) == _lib.HALO_E_INVAL  # ops not 16-byte aligned
     assert L.halo_tx_fixup_batch_device(b.data_ptr(), b.data_ptr(), b.data_ptr(), 1, b.data_ptr(), 2, 0, None,
                                         None) == _lib.HALO_E_INVAL  # unknown flag bit
-
-
-def _random_ops(n, seed):
-    from halo_amd import protocol
-
-    rng = np.random.default_rng(seed)
-    ops = protocol.tx_ops(n)
-    ops["steps"] = rng.integers(0, 32, n, dtype=np.uint8)
-    ops["dst_ip"] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-    ops["src_ip"] = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-    ops["dst_port"] = rng.integers(0, 1 << 16, n, dtype=np.uint32).astype(np.uint16)
-    ops["src_port"] = rng.integers(0, 1 << 16, n, dtype=np.uint32).astype(np.uint16)
-    return ops
 
 
 @pytest.mark.parametrize("size_mode,proto_mode,length,hint", [(0, 0, 64, 64), (1, 3, 0, 1514), (0, 3, 9000, 9014),

@@ -21,6 +21,12 @@ def test_edge_case(name):
     K.CASES[name](make)
 
 
+@pytest.mark.parametrize("name", sorted(K.SCALE_CASES))
+def test_scale_case(name):
+    """The expectations of tests/test_gpu_scale.py's switch cases, proven in host mode first."""
+    K.SCALE_CASES[name](make)
+
+
 def test_random_differential():
     K.differential(make, calls=60, max_n=300, seed=11)
     K.differential(make, calls=30, max_n=200, seed=12, pool_size=60, capacity=7)
