@@ -6,9 +6,11 @@ the thin Python host side over that ABI (ctypes). See DESIGN.md.
 """
 from . import _lib  # noqa: F401  (raises if libhalo_rx.so is not built: no CPU fallback)
 from ._lib import ACTION, ACTION_NAMES, RESULT_DTYPE, STATUS, STATUS_NAMES, NetIf, HaloError  # noqa: F401
+from ._lib import EGRESS_PORT_DTYPE  # noqa: F401
 from .arp import ArpTable  # noqa: F401
+from .egress import EgressResult, egress_arp, egress_host, egress_masks, egress_switch  # noqa: F401
 from .nat import NatTable  # noqa: F401
 from .switch import Switch  # noqa: F401
 
 __all__ = ["ACTION", "ACTION_NAMES", "RESULT_DTYPE", "STATUS", "STATUS_NAMES", "NetIf", "HaloError", "ArpTable", "NatTable",
-           "Switch"]
+           "Switch", "EGRESS_PORT_DTYPE", "EgressResult", "egress_arp", "egress_host", "egress_masks", "egress_switch"]

@@ -142,6 +142,11 @@ ARP_V = {name: code for code, name in enumerate(ARP_VERDICT_NAMES)}
 ARP_V_COUNT = len(ARP_VERDICT_NAMES)
 ARP_MAX_NETIFS = 64
 ARP_AGE, ARP_REFRESH_AHEAD = 300, 10
+# the egress step: halo_egress_port_t (24 bytes), HALO_EGRESS_KIND_*
+EGRESS_PORT_DTYPE = np.dtype([("frames", "<u4"), ("frames_written", "<u4"), ("bytes", "<u8"), ("bytes_written", "<u8")])
+assert EGRESS_PORT_DTYPE.itemsize == 24
+EGRESS_MAX_PORTS = 64
+EGRESS_KIND_MASKS, EGRESS_KIND_ARP, EGRESS_KIND_SWITCH = 0, 1, 2
 # halo_rx_ring_scan_t (24 bytes) and HALO_RING_STOP_* / HALO_RING_REGISTER
 RING_SCAN_DTYPE = np.dtype([("n_frames", "<u4"), ("stop", "<u4"), ("end_bytes", "<u8"), ("max_len", "<u4"),
                             ("pad", "<u4")])
@@ -263,6 +268,16 @@ class ArpConfig(ctypes.Structure):
 
     _fields_ = [("n_netifs", ctypes.c_uint32), ("netif", NetIf * 64), ("capacity", ctypes.c_uint32),
                 ("slots_log2", ctypes.c_uint32)]
+
+
+class EgressConfig(ctypes.Structure):
+    """halo_egress_config_t."""
+
+    _fields_ = [("n_ports", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("region_bytes", ctypes.c_uint64),
+                ("index_cap", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(EgressConfig) == 24
 
 
 class BatchDesc(ctypes.Structure):
@@ -415,6 +430,21 @@ _PROTOS = {
     "halo_ring_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
     "halo_ring_write_batch": (ctypes.c_int, [
         ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_ring_write_span": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),
+    "halo_tx_egress_workspace": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    "halo_tx_egress_masks_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64,
+        ctypes.c_void_p]),
+    "halo_tx_egress_arp_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64,
+        ctypes.c_void_p]),
+    "halo_tx_egress_switch_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p, _u8p,
+        ctypes.c_uint64, ctypes.c_void_p]),
+    "halo_tx_egress_host": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p,
+        _u8p]),
     "halo_synth_layout": (ctypes.c_int, [
         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint64)]),

@@ -447,3 +447,57 @@ extern "C" HALO_API int halo_ring_write_batch(void* memory, const uint8_t* bytes
     if (written) *written = count;
     return HALO_OK;
 }
+
+// A span of whole records (one port's egress stream) published at once: the records WritePacket
+// would write one by one, with one release store of head.
+extern "C" HALO_API int halo_ring_write_span(void* ring_memory, const uint8_t* span, uint64_t span_bytes,
+                                             uint32_t* records_written, uint64_t* bytes_written) {
+    uint64_t size = 0, tail_unused = 0;
+    uint8_t* m = static_cast<uint8_t*>(ring_memory);
+    if (!m || (reinterpret_cast<uintptr_t>(m) & 7u)) return HALO_E_INVAL;
+    uint64_t stored;
+    memcpy(&stored, m + 88, 8);
+    int rc = halo::validate_ring(m, (int64_t)(reinterpret_cast<uintptr_t>(m + halo::kRbHeader) - stored), &size,
+                                 &tail_unused);
+    if (rc) return rc;
+    if (span_bytes && !span) return HALO_E_INVAL;
+    for (uint64_t pos = 0; pos < span_bytes;) {  // every header, before a byte is written
+        if (span_bytes - pos < 4) return HALO_E_INVAL;
+        uint32_t len;
+        memcpy(&len, span + pos, 4);
+        const uint64_t total = (4ull + len + 3ull) & ~3ull;
+        if (len == 0 || (uint64_t)len > size / 2 || total > span_bytes - pos) return HALO_E_INVAL;
+        pos += total;
+    }
+    uint64_t* head_p = reinterpret_cast<uint64_t*>(m);
+    const uint64_t* tail_p = reinterpret_cast<const uint64_t*>(m + 64);
+    uint8_t* data = m + halo::kRbHeader;
+    const uint64_t mask = size - 1;
+    const uint64_t head = __atomic_load_n(head_p, __ATOMIC_RELAXED);  // this process is the producer
+    uint64_t tail = __atomic_load_n(tail_p, __ATOMIC_ACQUIRE);
+    uint64_t used = head - tail;
+    if (used > size || size - used < span_bytes) {  // short: look once more, as WritePacket does
+        tail = __atomic_load_n(tail_p, __ATOMIC_ACQUIRE);
+        used = head - tail;
+    }
+    const uint64_t room = used <= size && !(tail & 3u) ? size - used : 0;
+    uint64_t take = 0;
+    uint32_t count = 0;
+    while (take < span_bytes) {  // the longest prefix of whole records that fits
+        uint32_t len;
+        memcpy(&len, span + take, 4);
+        const uint64_t total = (4ull + len + 3ull) & ~3ull;
+        if (total > room - take) break;
+        take += total;
+        ++count;
+    }
+    if (take) {
+        const uint64_t pos = head & mask, first = size - pos < take ? size - pos : take;
+        memcpy(data + pos, span, first);
+        if (first < take) memcpy(data, span + first, take - first);
+        __atomic_store_n(head_p, head + take, __ATOMIC_RELEASE);
+    }
+    if (records_written) *records_written = count;
+    if (bytes_written) *bytes_written = take;
+    return HALO_OK;
+}

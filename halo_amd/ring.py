@@ -62,6 +62,17 @@ class RingBuffer:
         _lib.check("halo_ring_write_batch", rc)
         return int(written.value)
 
+    def write_span(self, span: np.ndarray):
+        """Publish a run of whole records (one port's egress stream, ``EgressResult.stream(p)``)
+        with one release store of head: (records written, bytes written) — the longest prefix that
+        fits the ring's free space. A malformed span raises and writes nothing."""
+        span = np.ascontiguousarray(span, dtype=np.uint8)
+        recs, taken = ctypes.c_uint32(), ctypes.c_uint64()
+        rc = _lib.lib.halo_ring_write_span(self.mem.ctypes.data, _lib.ptr(span), span.nbytes, ctypes.byref(recs),
+                                           ctypes.byref(taken))
+        _lib.check("halo_ring_write_span", rc)
+        return int(recs.value), int(taken.value)
+
     def write(self, frames) -> int:
         frames = [bytes(f) for f in frames]
         if not frames:

@@ -854,8 +854,9 @@ HALO_API int halo_nat_lookup_quote_device(const halo_nat_table_t* t, const halo_
  *      else FLOOD to every other port of the ingress port's VLAN (halo_switch_flood_mask). The
  *      lookup sees what frames 0..i learned. Age is not checked: only halo_switch_expire removes.
  *   5. tx_len = BuildEthFrm's length, max(len, 60), for a forwarded frame; 0 for a dropped one.
- * Only bytes 0-13 of a frame and its length are read. Not covered: copying or padding the frame
- * bytes to egress buffers, per-egress-port index lists, batches that mix ingress ports, VLAN tags.
+ * Only bytes 0-13 of a frame and its length are read. The frame bytes reach per-port transmit
+ * streams, padded, through halo_tx_egress_switch_device ("egress" below). Not covered: batches that
+ * mix ingress ports, VLAN tags.
  *
  * A switch is either a host switch (cfg.device = -1: host pointers, the sequential loop, `stream`
  * ignored) or a device switch (cfg.device >= 0: device pointers; table, entry count and scratch
@@ -965,9 +966,10 @@ HALO_API int halo_switch_debug_set_epoch(halo_switch_t* sw, uint32_t epoch);
  * FAILURE: argument errors (HALO_E_INVAL / _RANGE) leave the table as it was; a malformed ARP
  * message is data (its verdict). A library built without the device side answers HALO_E_NODEV to
  * the *_device calls.
- * Not covered: halo_tx_build_desc_t.dst_mac of locally originated packets; zero-padding a forwarded
- * frame to 60 bytes in place (tx_len tells the caller: frames are packed at 4-byte boundaries and
- * the padding would overwrite a neighbour); per-egress index lists; NatPortMappingFlowTable;
+ * A forwarded frame is not padded in place (frames are packed at 4-byte boundaries and the padding
+ * would overwrite a neighbour): tx_len tells the caller, and halo_tx_egress_arp_device ("egress"
+ * below) writes the padded copy and the per-port index lists.
+ * Not covered: halo_tx_build_desc_t.dst_mac of locally originated packets; NatPortMappingFlowTable;
  * compact records in the gather; DHCP. */
 typedef struct halo_arp_table halo_arp_table_t;
 #define HALO_ARP_MAX_NETIFS 64u
@@ -1114,6 +1116,105 @@ HALO_API int halo_arp_gather_device(const uint8_t* d_bytes, const uint32_t* d_of
                                     const halo_rx_result_t* d_records, uint32_t n, uint32_t netif,
                                     halo_arp_msg_t* d_msgs, uint32_t cap, uint32_t* d_count, void* d_workspace,
                                     uint64_t workspace_bytes, halo_stream_t stream);
+
+/* ---- egress: per-port transmit streams in ring-record form -----------------------------------
+ * The forward path's last step: TxEthernet -> BuildEthFrm (zero-pad to 60 bytes) -> EthTxFunc ->
+ * RingBufferProducer.WritePacket into the egress port's tx ring (engine/ethernet_engine.go:34-49,
+ * :117-129, protocol/ethernet.go:58-82, dpdk/dpdk.go:202-213, mem/ring_buffer.go:249-295). A stable
+ * multi-way partition of a device-resident ragged batch into one contiguous byte stream per egress
+ * port: port p's stream starts at d_out + p * region_bytes and holds the port's frames in ascending
+ * frame index, each laid out exactly as one ring record:
+ *   u32 little-endian tx_len = max(len, 60); the frame's len bytes; zeros up to tx_len (BuildEthFrm's
+ *   padding); zeros up to the next 4-byte boundary. Record size = (4 + tx_len + 3) & ~3.
+ * WritePacket leaves the alignment bytes unwritten; zero is this build's definition, so that outputs
+ * compare whole. halo_ring_write_span then publishes a stream into a tx ring with one or two copies
+ * and one release store of head.
+ *
+ * WHICH PORTS a frame goes to (bits at or above n_ports are ignored everywhere):
+ *   masks:  bit p of d_masks[i].
+ *   arp:    verdict == HALO_ARP_V_HIT -> port out_netif; every other verdict -> nowhere.
+ *   switch: UNICAST -> out_port (which may be the ingress port, as in the reference); FLOOD -> every
+ *           bit of flood_mask, the value halo_switch_flood_mask gives for the batch's ingress port;
+ *           every other verdict -> nowhere. The order among the ports of a flood is not observable
+ *           (the streams are separate; the reference iterates a Go map there).
+ * SENDABLE: 14 <= len <= 1514 (9014 with HALO_RX_JUMBO_EXT): BuildEthFrm refuses a payload over 1500
+ *   bytes and TxEthernet then sends nothing. A frame selected for at least one port below n_ports
+ *   but not sendable is emitted nowhere and counted once in *d_skipped (optional, INCREMENTED).
+ * REGION OVERFLOW (build-defined): port p's records are written while they fit wholly in
+ *   region_bytes; the first record that does not fit ends the port's written prefix. `frames` and
+ *   `bytes` are still the totals, as halo_arp_gather_device's *d_count is beyond `cap`, so the caller
+ *   can resubmit the tail. (WritePacket on a full ring drops one frame and may take a later, shorter
+ *   one.)
+ * INDEX LISTS: d_index[p * index_cap + k] = the batch index of port p's k-th record; the first
+ *   min(frames, index_cap) entries per port are written, also for records beyond the region.
+ * READS: nothing of a frame that is not selected and sendable; nothing past the 4-byte word that
+ *   holds a selected frame's last byte, and the bytes of that word beyond len (a neighbour's, or a
+ *   gap's) do not reach the output. The input batch is never written.
+ * WRITES: exactly [p * region_bytes, p * region_bytes + bytes_written) of each port, the n_ports
+ *   summaries, the index entries above, *d_skipped; nothing else.
+ * The device calls are asynchronous on `stream` with no host round trip: three launches (per-tile
+ * counts, a scan over tiles, the scatter). n == 0 is OK and zeroes the summaries. Every argument is
+ * checked before any device call. HALO_E_INVAL: a null cfg / d_ports, a null array with n > 0,
+ * n_ports outside 1..64, flags other than HALO_RX_JUMBO_EXT, region_bytes not a multiple of 16,
+ * d_out null with region_bytes > 0 or not 16-byte aligned, d_index null with index_cap > 0, a
+ * misaligned array (offsets, index, skipped: 4; lens: 2; masks, arp results, summaries, workspace: 8;
+ * switch results: 4), workspace_bytes < halo_tx_egress_workspace(n, n_ports). HALO_E_NODEV / _ARCH
+ * as elsewhere. */
+#define HALO_EGRESS_MAX_PORTS 64u
+#define HALO_EGRESS_KIND_MASKS 0u  /* halo_tx_egress_host's `kind`: selectors are uint64_t masks  */
+#define HALO_EGRESS_KIND_ARP 1u    /* ... halo_arp_result_t                                        */
+#define HALO_EGRESS_KIND_SWITCH 2u /* ... halo_sw_result_t, with flood_mask                        */
+typedef struct halo_egress_port { /* SET by the call, one per port */
+    uint32_t frames;         /* records selected for the port, also beyond the region */
+    uint32_t frames_written; /* the prefix of them that fits the region wholly        */
+    uint64_t bytes;          /* sum of their record sizes                             */
+    uint64_t bytes_written;  /* <= region_bytes; a whole number of records            */
+} halo_egress_port_t;        /* 24 B */
+typedef struct halo_egress_config {
+    uint32_t n_ports;      /* 1..64                                                                  */
+    uint32_t flags;        /* HALO_RX_JUMBO_EXT lifts the 1514-byte cap to 9014, as elsewhere        */
+    uint64_t region_bytes; /* port p's stream starts at d_out + p * region_bytes; a multiple of 16
+                              for the device calls                                                   */
+    uint32_t index_cap;    /* entries per port in d_index (0 with d_index NULL)                      */
+    uint32_t reserved;     /* 0                                                                      */
+} halo_egress_config_t;    /* 24 B */
+/* Bytes of device workspace (8-byte aligned) a call over n frames and n_ports ports needs; 0 for
+ * n_ports outside 1..64. One workspace serves any number of calls issued on one stream. */
+HALO_API uint64_t halo_tx_egress_workspace(uint32_t n, uint32_t n_ports);
+HALO_API int halo_tx_egress_masks_device(const halo_egress_config_t* cfg, const uint8_t* d_bytes,
+                                         const uint32_t* d_offsets_dw, const uint16_t* d_lens, uint32_t n,
+                                         const uint64_t* d_masks, uint8_t* d_out, halo_egress_port_t* d_ports,
+                                         uint32_t* d_index, uint32_t* d_skipped, void* d_workspace,
+                                         uint64_t workspace_bytes, halo_stream_t stream);
+/* After halo_arp_encap_device in stream order: HIT frames carry the rewritten MACs. */
+HALO_API int halo_tx_egress_arp_device(const halo_egress_config_t* cfg, const uint8_t* d_bytes,
+                                       const uint32_t* d_offsets_dw, const uint16_t* d_lens, uint32_t n,
+                                       const halo_arp_result_t* d_results, uint8_t* d_out,
+                                       halo_egress_port_t* d_ports, uint32_t* d_index, uint32_t* d_skipped,
+                                       void* d_workspace, uint64_t workspace_bytes, halo_stream_t stream);
+/* After halo_switch_forward (a device switch) in stream order. */
+HALO_API int halo_tx_egress_switch_device(const halo_egress_config_t* cfg, const uint8_t* d_bytes,
+                                          const uint32_t* d_offsets_dw, const uint16_t* d_lens, uint32_t n,
+                                          const halo_sw_result_t* d_results, uint64_t flood_mask, uint8_t* d_out,
+                                          halo_egress_port_t* d_ports, uint32_t* d_index, uint32_t* d_skipped,
+                                          void* d_workspace, uint64_t workspace_bytes, halo_stream_t stream);
+/* The same outputs from the sequential loop over host memory; no HIP. `kind` = HALO_EGRESS_KIND_*
+ * says what `selectors` points to; flood_mask is read for the switch kind only. The caller picks
+ * it by name for polls at the reference's cadence, as the switch's host mode is picked. `out`
+ * needs no alignment and region_bytes may be any value here. */
+HALO_API int halo_tx_egress_host(const halo_egress_config_t* cfg, uint32_t kind, const uint8_t* bytes,
+                                 const uint32_t* offsets_dw, const uint16_t* lens, uint32_t n, const void* selectors,
+                                 uint64_t flood_mask, uint8_t* out, halo_egress_port_t* ports, uint32_t* index,
+                                 uint32_t* skipped);
+/* Publish a span of whole records (host memory, as one port's stream) into a ring made by
+ * halo_ring_create. Every header is validated first: a length of 0, a length above size / 2 or a
+ * record running past span_bytes returns HALO_E_INVAL with nothing written. The longest prefix of
+ * records that fits the ring's free space is taken (tail is re-read once when short, as WritePacket
+ * does), copied in stream order — positions are taken modulo the size, so the ring bytes are those
+ * WritePacket would leave, plus the zero alignment bytes — and head is published once with a release
+ * store. *records_written / *bytes_written (optional) say what was taken. Host only. */
+HALO_API int halo_ring_write_span(void* ring_memory, const uint8_t* span, uint64_t span_bytes,
+                                  uint32_t* records_written, uint64_t* bytes_written);
 
 /* ---- the reference engine's per-frame decision (engine/ethernet_engine.go:13-31,
  *      engine/ipv4_engine.go:18-47, engine/{udp,tcp,icmp}_engine.go) ------------------ */
