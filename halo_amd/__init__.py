@@ -10,7 +10,9 @@ from ._lib import EGRESS_PORT_DTYPE  # noqa: F401
 from .arp import ArpTable  # noqa: F401
 from .egress import EgressResult, egress_arp, egress_host, egress_masks, egress_switch  # noqa: F401
 from .nat import NatTable  # noqa: F401
+from .respond import RespondResult, build_replies, respond, respond_host, tcp_port_map  # noqa: F401  (adds ArpTable.encap_tx)
 from .switch import Switch  # noqa: F401
 
 __all__ = ["ACTION", "ACTION_NAMES", "RESULT_DTYPE", "STATUS", "STATUS_NAMES", "NetIf", "HaloError", "ArpTable", "NatTable",
-           "Switch", "EGRESS_PORT_DTYPE", "EgressResult", "egress_arp", "egress_host", "egress_masks", "egress_switch"]
+           "Switch", "EGRESS_PORT_DTYPE", "EgressResult", "egress_arp", "egress_host", "egress_masks", "egress_switch",
+           "RespondResult", "build_replies", "respond", "respond_host", "tcp_port_map"]

@@ -147,6 +147,12 @@ EGRESS_PORT_DTYPE = np.dtype([("frames", "<u4"), ("frames_written", "<u4"), ("by
 assert EGRESS_PORT_DTYPE.itemsize == 24
 EGRESS_MAX_PORTS = 64
 EGRESS_KIND_MASKS, EGRESS_KIND_ARP, EGRESS_KIND_SWITCH = 0, 1, 2
+# the local responders: halo_respond_src_t (8 bytes), HALO_RESPOND_*
+RESPOND_SRC_DTYPE = np.dtype([("index", "<u4"), ("kind", "u1"), ("pad", "u1", (3,))])
+assert RESPOND_SRC_DTYPE.itemsize == 8
+RESPOND_KIND_NAMES = ("ECHO", "TTL", "TCP_SYN", "TCP_SYNACK")
+RESPOND_KIND = {name: code for code, name in enumerate(RESPOND_KIND_NAMES)}
+RESPOND_KIND_COUNT = len(RESPOND_KIND_NAMES)
 # halo_rx_ring_scan_t (24 bytes) and HALO_RING_STOP_* / HALO_RING_REGISTER
 RING_SCAN_DTYPE = np.dtype([("n_frames", "<u4"), ("stop", "<u4"), ("end_bytes", "<u8"), ("max_len", "<u4"),
                             ("pad", "<u4")])
@@ -445,6 +451,16 @@ _PROTOS = {
     "halo_tx_egress_host": (ctypes.c_int, [
         ctypes.c_void_p, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p,
         _u8p]),
+    "halo_arp_encap_tx_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p,
+        ctypes.c_void_p]),
+    "halo_tx_respond_workspace": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "halo_tx_respond_device": (ctypes.c_int, [
+        _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(NetIf), _u8p, _u8p, _u8p, _u8p, _u8p, _u8p,
+        _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64, ctypes.c_void_p]),
+    "halo_tx_respond_host": (ctypes.c_int, [
+        _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(NetIf), _u8p, _u8p, _u8p, _u8p, _u8p, _u8p,
+        _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     "halo_synth_layout": (ctypes.c_int, [
         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint64)]),

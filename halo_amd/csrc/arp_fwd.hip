@@ -110,9 +110,14 @@ __global__ void __launch_bounds__(256) arp_lookup_kernel(const ArpView v, const 
     if ((threadIdx.x & 63u) == 0 && misses) atomicAdd(miss_count, misses);
 }
 
+// kTx = false: the forward path's step, in_arg = the in NetIf's nat_enable. kTx = true: TxIpv4's
+// (engine/ipv4_engine.go:50-99) for frames NetIf in_arg originated: a x.x.x.255 destination goes
+// out of that NetIf to the broadcast MAC without a route, and dst == the out NetIf's address is a
+// LOOPBACK whatever nat_enable says. The forward instantiation holds none of the Tx branches.
+template <bool kTx>
 __global__ void __launch_bounds__(256) arp_encap_kernel(const ArpView v, uint8_t* bytes, const uint32_t* __restrict__ offsets_dw,
                                                         const uint16_t* __restrict__ lens, uint32_t n,
-                                                        const uint32_t* __restrict__ route_ids, uint32_t in_nat,
+                                                        const uint32_t* __restrict__ route_ids, uint32_t in_arg,
                                                         const uint8_t* __restrict__ select, uint2* __restrict__ results,
                                                         uint32_t* counts, uint32_t* miss_count) {
     __shared__ uint32_t s_counts[HALO_ARP_V_COUNT];
@@ -136,6 +141,14 @@ __global__ void __launch_bounds__(256) arp_encap_kernel(const ArpView v, uint8_t
                 const uint32_t w3 = p[3], w7 = p[7], h = *reinterpret_cast<const uint16_t*>(f + 32);
                 const uint2 r = routed ? *reinterpret_cast<const uint2*>(v.routes + rid) : make_uint2(0u, 0xFFFFFFFFu);
                 if ((w3 & 0xFFFFu) != 0x0008u) {  // bytes 12-13 are not 08 00
+                } else if (kTx && (h >> 8) == 255u) {  // :60-61, :85-86: no FindRoute, no GetArpCache
+                    out = in_arg;
+                    const uint4 nif = *reinterpret_cast<const uint4*>(v.netifs + out);
+                    verdict = HALO_ARP_V_HIT;
+                    tx = len < 60u ? 60u : len;
+                    p[0] = 0xFFFFFFFFu;
+                    p[1] = 0xFFFFu | nif.y << 16;
+                    p[2] = nif.y >> 16 | nif.z << 16;
                 } else if (rid == HALO_ROUTE_NONE) {
                     verdict = HALO_ARP_V_NO_ROUTE;
                 } else if (rid == HALO_ROUTE_PANIC) {
@@ -146,7 +159,7 @@ __global__ void __launch_bounds__(256) arp_encap_kernel(const ArpView v, uint8_t
                         const uint4 nif = *reinterpret_cast<const uint4*>(v.netifs + out);  // ip, mac_lo, mac_hi, nat
                         // ipv4DstAddr is a slice into the packet: bytes 30-33 as they are now
                         const uint32_t dst = ((w7 >> 16) & 0xFFu) << 24 | (w7 >> 24) << 16 | (h & 0xFFu) << 8 | h >> 8;
-                        if (dst == nif.x && !in_nat) {
+                        if (dst == nif.x && (kTx || !in_arg)) {
                             verdict = HALO_ARP_V_LOOPBACK;
                         } else {
                             target = r.x ? r.x : dst;
@@ -434,7 +447,7 @@ int ops_lookup(const halo_arp_table* t, const uint32_t* d_ips, const uint8_t* d_
 }
 
 int ops_encap(const halo_arp_table* t, uint8_t* d_bytes, const uint32_t* d_offsets_dw, const uint16_t* d_lens, uint32_t n,
-              const uint32_t* d_route_ids, uint32_t in_netif, const uint8_t* d_select, halo_arp_result_t* d_results,
+              const uint32_t* d_route_ids, uint32_t in_netif, bool tx, const uint8_t* d_select, halo_arp_result_t* d_results,
               uint32_t* d_counts, uint32_t* d_miss_count, halo_stream_t stream) {
     ArpDevice* d = dev_of(t);
     if (!d) return HALO_E_INVAL;  // never synced
@@ -451,9 +464,14 @@ int ops_encap(const halo_arp_table* t, uint8_t* d_bytes, const uint32_t* d_offse
     if ((reinterpret_cast<uintptr_t>(d_lens) & 1u) || (reinterpret_cast<uintptr_t>(d_results) & 7u)) return HALO_E_INVAL;
     const int rc = check_device();
     if (rc) return rc;
-    hipLaunchKernelGGL(arp_encap_kernel, dim3(arp_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), v, d_bytes,
-                       d_offsets_dw, d_lens, n, d_route_ids, t->cfg.netif[in_netif].nat_enable ? 1u : 0u, d_select,
-                       reinterpret_cast<uint2*>(d_results), d_counts, d_miss_count);
+    if (tx)
+        hipLaunchKernelGGL(arp_encap_kernel<true>, dim3(arp_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), v,
+                           d_bytes, d_offsets_dw, d_lens, n, d_route_ids, in_netif, d_select,
+                           reinterpret_cast<uint2*>(d_results), d_counts, d_miss_count);
+    else
+        hipLaunchKernelGGL(arp_encap_kernel<false>, dim3(arp_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), v,
+                           d_bytes, d_offsets_dw, d_lens, n, d_route_ids, t->cfg.netif[in_netif].nat_enable ? 1u : 0u,
+                           d_select, reinterpret_cast<uint2*>(d_results), d_counts, d_miss_count);
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }
 

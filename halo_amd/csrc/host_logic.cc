@@ -8,6 +8,8 @@
 #include <algorithm>
 #include <iterator>
 
+#include "rx_dispatch.h"
+
 namespace halo {
 
 bool pow2(uint64_t x) { return x >= 8 && (x & (x - 1)) == 0; }
@@ -303,41 +305,13 @@ uint16_t ethertype_of(const halo_rx_record16_t& r) {
     }
 }
 
-uint8_t local_action(uint8_t ip_proto) {
-    return ip_proto == halo::kIpIcmp ? HALO_RX_ACT_LOCAL_ICMP
-         : ip_proto == halo::kIpUdp  ? HALO_RX_ACT_LOCAL_UDP
-                                     : HALO_RX_ACT_LOCAL_TCP;
-}
-
 template <typename Rec>
 int dispatch(const Rec* results, uint32_t n, const halo_rx_netif_t* netif, uint8_t* actions, uint32_t* action_hist) {
     if (n && (!results || !netif || !actions)) return HALO_E_INVAL;
     for (uint32_t i = 0; i < n; ++i) {
         const Rec& r = results[i];
-        const uint16_t ethertype = ethertype_of(r);
-        uint8_t a;
-        if (r.status == HALO_RX_ETH_LEN || r.status == HALO_RX_ETH_TYPE) {
-            a = HALO_RX_ACT_DROP_ETH;                        // ethernet_engine.go:18-21
-        } else if (!(r.flags & HALO_RX_F_MAC_MATCH)) {
-            a = HALO_RX_ACT_IGNORE_MAC;                      // ethernet_engine.go:22
-        } else if (ethertype == halo::kEthArp) {
-            a = HALO_RX_ACT_ARP;                             // ethernet_engine.go:24-25
-        } else if (ethertype != halo::kEthIpv4) {
-            a = HALO_RX_ACT_IGNORE_TYPE;                     // ethernet_engine.go:28
-        } else if (r.status >= HALO_RX_IP_LEN && r.status <= HALO_RX_IP_TOTLEN_OVERRUN) {
-            a = HALO_RX_ACT_DROP_IP;                         // ipv4_engine.go:19-23
-        } else if (r.flags & HALO_RX_F_IP_BCAST) {           // ipv4_engine.go:24-30
-            if (r.ip_proto == halo::kIpUdp)
-                a = r.status == HALO_RX_OK ? HALO_RX_ACT_BCAST_UDP : HALO_RX_ACT_DROP_BCAST_UDP;
-            else
-                a = HALO_RX_ACT_IGNORE_BCAST;
-        } else if (!(r.flags & HALO_RX_F_DST_IS_OWN) || netif->nat_enable) {
-            a = HALO_RX_ACT_FORWARD;                         // ipv4_engine.go:31-37
-        } else if (r.status != HALO_RX_OK) {
-            a = HALO_RX_ACT_DROP_L4;                         // {udp,tcp,icmp}_engine.go Rx*
-        } else {
-            a = local_action(r.ip_proto);                    // ipv4_engine.go:38-46
-        }
+        // the decision itself is rx_dispatch.h's, which the responder kernels share
+        const uint8_t a = halo::action_of(r.status, r.flags, ethertype_of(r), r.ip_proto, netif->nat_enable != 0);
         actions[i] = a;
         if (action_hist) ++action_hist[a];
     }
@@ -362,16 +336,7 @@ extern "C" HALO_API int halo_rx_dispatch_loopback(const halo_rx_result_t* result
     if (n && (!results || !netif || !actions)) return HALO_E_INVAL;
     for (uint32_t i = 0; i < n; ++i) {
         const halo_rx_result_t& r = results[i];
-        uint8_t a;
-        if (r.status >= HALO_RX_ETH_LEN && r.status <= HALO_RX_IP_TOTLEN_OVERRUN) {
-            a = HALO_RX_ACT_DROP_IP;                         // engine.go:362-365 (no Ethernet layer)
-        } else if (!(r.flags & HALO_RX_F_DST_IS_OWN)) {
-            a = HALO_RX_ACT_LO_NOT_OWN;                      // engine.go:366-368
-        } else if (r.status != HALO_RX_OK) {
-            a = HALO_RX_ACT_DROP_L4;                         // Rx{Icmp,Udp,Tcp} log and drop
-        } else {
-            a = local_action(r.ip_proto);                    // engine.go:369-376
-        }
+        const uint8_t a = halo::action_of_loopback(r.status, r.flags, r.ip_proto);
         actions[i] = a;
         if (action_hist) ++action_hist[a];
     }

@@ -544,8 +544,9 @@ HALO_API int halo_tx_icmp_deep_nat_batch_device(uint8_t* d_bytes, const uint32_t
  *       protocol.BuildEthFrm        protocol/ethernet.go:58-82 (src MAC = the NetIf's, pad to 60 B)
  * `flags & HALO_RX_CSUM_ENABLE` is protocol.CheckSumEnable: it gates the IPv4 header, UDP and
  * TCP checksums (0 when off); the ICMP checksum is always filled (icmp.go:84-87). TxIpv4's
- * control-plane decisions (FindRoute, the ARP cache, broadcast) are the caller's: each
- * descriptor carries the destination MAC they produced and its mode:
+ * control-plane decisions (FindRoute, the ARP cache, broadcast) are the caller's — or, on the
+ * device, halo_arp_encap_tx_device's over the built frames ("local responders" below): each
+ * descriptor carries the destination MAC they produced (zeros when that call fills it) and its mode:
  *   HALO_TX_BUILD_ETH       the Ethernet frame TxEthernet hands to EthTxFunc
  *   HALO_TX_BUILD_LOOPBACK  the IPv4 packet alone: the copy TxIpv4 puts into the NetIf's LoChan
  *                           when the destination is its own address (engine/ipv4_engine.go:72-79),
@@ -969,8 +970,10 @@ HALO_API int halo_switch_debug_set_epoch(halo_switch_t* sw, uint32_t epoch);
  * A forwarded frame is not padded in place (frames are packed at 4-byte boundaries and the padding
  * would overwrite a neighbour): tx_len tells the caller, and halo_tx_egress_arp_device ("egress"
  * below) writes the padded copy and the per-port index lists.
- * Not covered: halo_tx_build_desc_t.dst_mac of locally originated packets; NatPortMappingFlowTable;
- * compact records in the gather; DHCP. */
+ * Locally originated packets take TxIpv4's variant of the step, halo_arp_encap_tx_device, on the
+ * frames halo_tx_build_batch_device built ("local responders" below).
+ * Not covered: Router.Ipv4PktFwdHook; NatPortMappingFlowTable; compact records in the gather; DHCP;
+ * UDP service replies (the handlers' job); sending the LoChan copy of a LOOPBACK. */
 typedef struct halo_arp_table halo_arp_table_t;
 #define HALO_ARP_MAX_NETIFS 64u
 #define HALO_ARP_AGE 300u          /* SetArpCache: ExpTime = now + 300             */
@@ -1105,6 +1108,20 @@ HALO_API int halo_arp_encap_device(const halo_arp_table_t* t, uint8_t* d_bytes, 
                                    const uint16_t* d_lens, uint32_t n, const uint32_t* d_route_ids,
                                    uint32_t in_netif, const uint8_t* d_select, halo_arp_result_t* d_results,
                                    uint32_t* d_counts, uint32_t* d_miss_count, halo_stream_t stream);
+/* TxIpv4's L3 / L2 step (engine/ipv4_engine.go:50-99) for frames NetIf `self_netif` originated —
+ * the slots halo_tx_build_batch_device filled, with the route id FindRoute(dst) returned for each.
+ * Arguments, outputs, counters and errors are halo_arp_encap_device's, with two differences:
+ *   a destination whose last byte (frame byte 33) is 255: the route id is not consulted; HIT,
+ *     out_netif = self_netif, bytes 0-5 = ff x 6, bytes 6-11 = netif[self_netif].mac, tx_len =
+ *     max(len, 60), target_ip = 0 (:60-61, :85-86, :92-93);
+ *   otherwise dst == netif[out].ip -> LOOPBACK whatever nat_enable says (:71-80). The LoChan copy,
+ *     exactly totalLen bytes from byte 14, stays the caller's.
+ * Everything else is unchanged: NONE (also a slot that was not built: length 0), NO_ROUTE,
+ * ROUTE_PANIC, OWN_IP, MISS, HIT and the exact bytes written. HALO_E_RANGE: self_netif >= n_netifs. */
+HALO_API int halo_arp_encap_tx_device(const halo_arp_table_t* t, uint8_t* d_bytes, const uint32_t* d_offsets_dw,
+                                      const uint16_t* d_lens, uint32_t n, const uint32_t* d_route_ids,
+                                      uint32_t self_netif, const uint8_t* d_select, halo_arp_result_t* d_results,
+                                      uint32_t* d_counts, uint32_t* d_miss_count, halo_stream_t stream);
 /* The ARP messages of a parsed batch: the records halo_rx_dispatch maps to HALO_RX_ACT_ARP (status
  * OK, EtherType 0x0806, MAC_MATCH) written densely to d_msgs (8-byte aligned) in ascending frame
  * index, with `netif` in every message. *d_count is SET to the number selected, also beyond `cap`;
@@ -1255,6 +1272,88 @@ HALO_API int halo_rx_dispatch_compact(const halo_rx_record16_t* records, uint32_
 HALO_API int halo_rx_dispatch_loopback(const halo_rx_result_t* results, uint32_t n,
                                        const halo_rx_netif_t* netif, uint8_t* actions,
                                        uint32_t* action_hist);
+
+/* ---- local responders: echo, time-exceeded and TCP handshake replies -------------------------
+ * The three answers the reference gives from inside its receive loop, for a parsed batch at once:
+ * from the records (and offsets_dw / lens) to one dense list of halo_tx_build_desc_t in ascending
+ * frame index — at most one reply per frame, and BuildIpv4Pkt's iphId++ runs in frame order — for
+ * halo_tx_build_batch_device to consume with d_payload = the batch's own d_bytes. No payload is
+ * copied and no frame byte is read. Per frame i, with a = halo_rx_dispatch's action of record i,
+ * the first row that holds, in the reference's order:
+ *   ECHO        a == LOCAL_ICMP and l4_aux == 8 (ICMP_REQUEST): RxIcmp answers TxIcmp(icmpPayload,
+ *               ICMP_REPLY, icmpId, icmpSeq, src) (engine/icmp_engine.go:12-23). proto 1, aux 0,
+ *               src_port = l4_seq >> 16 (the id), dst_port = l4_seq & 0xFFFF, payload = the
+ *               record's payload_off / payload_len.
+ *   ECHO        a == FORWARD, d_nat_verdict[i] == HALO_NAT_V_MISS, ip_proto == 1, status == OK,
+ *               l4_aux == 8: Ipv4RouteForward returned false on a NATing NetIf and RxIpv4 hands an
+ *               ICMP packet to RxIcmp (engine/ipv4_engine.go:31-36, :120-124). As above. Any other
+ *               frame with verdict MISS gets nothing: the forward ended before its TTL step.
+ *   TTL         a == FORWARD, ops[i].steps & HALO_TX_TTL and !(result[i] & HALO_TX_R_TTL_ALIVE):
+ *               TxIcmp(ethPayload[:28], ICMP_TTL, {0,0}, 0, src) (engine/ipv4_engine.go:133-142).
+ *               proto 1, aux 11, ports 0, payload = frame bytes [14, 14 + min(28, len - 14)) AS THE
+ *               FIXUP LEFT THEM (post-DNAT, TTL as HandleIpv4PktTtl left it): build after the fixup
+ *               in stream order.
+ *   TCP_SYN     a == LOCAL_TCP, bit dport of d_tcp_ports set (TcpServiceMap), SYN && !ACK: TxTcp(nil,
+ *               dport, sport, src, 1234567890, seq + 1, SYN|ACK) (engine/tcp_engine.go:16-21).
+ *               proto 6, aux 0x12, src_port = dport, dst_port = sport, seq = 1234567890, ack =
+ *               l4_seq + 1 (u32 wrap), payload length 0.
+ *   TCP_SYNACK  the same with SYN && ACK: aux 0x10, seq = 1234567891, ack = l4_seq + 1 (:22-23).
+ * Every kind: src_ip = netif->ip, dst_ip = the record's src_ip, payload_off = 4 * offsets_dw[i] +
+ * the offset above, dst_mac zeros, mode HALO_TX_BUILD_ETH, pads zero. ip_id, the checksums and the
+ * payload-length rejections stay halo_tx_build_batch_device's: an echo request above 1472 payload
+ * bytes (HALO_RX_JUMBO_EXT) is emitted here and rejected there, as BuildIcmpPkt would.
+ * d_nat_verdict (halo_nat_lookup_wan_device's), the pair d_ops / d_fixup_result
+ * (halo_tx_fixup_batch_device's) and d_tcp_ports (65,536 bits as 2,048 u32, bit p & 31 of word
+ * p >> 5) are each optional: an absent input means its rows never fire. Only one of d_ops and
+ * d_fixup_result is HALO_E_INVAL. `flags`: HALO_RX_L3_START or 0. With HALO_RX_L3_START the
+ * records are LoChan packets (engine/engine.go:353-381): the action is halo_rx_dispatch_loopback's,
+ * only the LOCAL_* rows apply, and payload_off is in packet coordinates.
+ * OUTPUTS: d_desc[k], d_src[k] = {frame index, kind} and d_dst_ip[k] (optional; what
+ * halo_route_lookup_device takes) for the first min(count, cap) replies; *d_count is SET to the
+ * total, also beyond `cap` (halo_arp_gather_device's convention); d_kind_counts (optional,
+ * HALO_RESPOND_KIND_COUNT u32) is INCREMENTED by the totals per kind; d_actions (optional, n bytes)
+ * = halo_rx_dispatch's (or _loopback's) action of every frame, a device-side dispatch. Nothing else
+ * is written: entries at and beyond min(count, cap) stay as they were.
+ * TxIpv4's L3 / L2 step for the built frames is halo_arp_encap_tx_device; the chain is respond ->
+ * halo_tx_build_batch_device (payload = the rx batch) -> halo_route_lookup_device(d_dst_ip) ->
+ * halo_arp_encap_tx_device -> halo_tx_egress_arp_device. A reply that then gets NO_ROUTE, MISS or
+ * OWN_IP has still consumed its iphId (BuildIpv4Pkt runs before FindRoute): build every descriptor,
+ * drop afterwards.
+ * Not covered: Router.Ipv4PktFwdHook; NatPortMappingFlowTable; DHCP; UDP service replies (the
+ * handlers' job); sending the LoChan copy of a LOOPBACK reply.
+ * The device call: three launches on `stream` (tile counts, scan, scatter), every argument checked
+ * before a device is looked for. Alignment: d_records 16; d_desc, d_src 8; offsets, ops, ports map,
+ * dst_ip, count, kind counts, workspace 4; lens 2. HALO_E_INVAL: null netif / d_count, a null
+ * array with n > 0, d_desc or d_src null with cap > 0, other flags, a short workspace. n == 0 is OK
+ * and sets *d_count = 0. */
+#define HALO_RESPOND_ECHO 0u
+#define HALO_RESPOND_TTL 1u
+#define HALO_RESPOND_TCP_SYN 2u
+#define HALO_RESPOND_TCP_SYNACK 3u
+#define HALO_RESPOND_KIND_COUNT 4u
+typedef struct halo_respond_src {
+    uint32_t index; /* the answered frame's index in its batch */
+    uint8_t kind;   /* HALO_RESPOND_*                          */
+    uint8_t pad[3];
+} halo_respond_src_t; /* 8 B */
+/* Bytes of device workspace (4-byte aligned, no initialisation) for n frames. One workspace serves
+ * any number of calls issued on one stream. */
+HALO_API uint64_t halo_tx_respond_workspace(uint32_t n);
+HALO_API int halo_tx_respond_device(const uint32_t* d_offsets_dw, const uint16_t* d_lens,
+                                    const halo_rx_result_t* d_records, uint32_t n, uint32_t flags,
+                                    const halo_rx_netif_t* netif, const uint8_t* d_nat_verdict,
+                                    const halo_tx_op_t* d_ops, const uint8_t* d_fixup_result,
+                                    const uint32_t* d_tcp_ports, halo_tx_build_desc_t* d_desc,
+                                    halo_respond_src_t* d_src, uint32_t* d_dst_ip, uint32_t cap, uint32_t* d_count,
+                                    uint32_t* d_kind_counts, uint8_t* d_actions, void* d_workspace,
+                                    uint64_t workspace_bytes, halo_stream_t stream);
+/* The same outputs from the sequential loop over host memory; no HIP. The caller picks it by name
+ * for polls at the reference's cadence. Arrays need only their natural alignment. */
+HALO_API int halo_tx_respond_host(const uint32_t* offsets_dw, const uint16_t* lens, const halo_rx_result_t* records,
+                                  uint32_t n, uint32_t flags, const halo_rx_netif_t* netif, const uint8_t* nat_verdict,
+                                  const halo_tx_op_t* ops, const uint8_t* fixup_result, const uint32_t* tcp_ports,
+                                  halo_tx_build_desc_t* desc, halo_respond_src_t* src, uint32_t* dst_ip, uint32_t cap,
+                                  uint32_t* count, uint32_t* kind_counts, uint8_t* actions);
 
 /* ---- synthetic traffic (bench + tests; SURVEY.md §8d generator) ----------------------
  * Every field of frame i is a pure function of (seed, i), so any shard of the global
