@@ -851,6 +851,14 @@ __device__ __forceinline__ void lane_window_store(const RxParams& p, uint32_t ba
     __builtin_amdgcn_wave_barrier();
 }
 
+// Tried and removed (HALO_RX_LANE_SPAN): a window whose 64 frames lie back to back
+// read as its 4096-byte span (four 1 KB rows per wave instead of four loads at a 64 B stride) and
+// transposed through a 5120 B LDS window at an odd pitch. The counters showed there was nothing to
+// win: the per-lane loads already cost one TCP->TCC request per 128 B line (35.1 per wave before and
+// after) and the same 168 TCP accesses per wave; the span added 8 LDS instructions and 63 LDS cycles
+// per wave. 1M x 64 B 18.74-18.91 -> 18.67-18.95 us, 4M 72.85-73.56 -> 72.38-73.62, 16M 279.9-282.7
+// -> 279.5-282.2 (five interleaved rounds, profiles/r10/ab_span_lean.log).
+
 // The whole window on the fast path, after frame_meta: false (nothing stored, st.buf not to be
 // used) when some frame of it is not plain.
 template <int FUSE, int ST>
@@ -930,6 +938,21 @@ __device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t b
     lane_window_store<ST>(p, base, lane, s_rec_w);
 }
 
+// HALO_RX_LANE_LEAN: a launch that keeps no status histogram (p.hist null, the
+// headline call) runs an instance with HIST false: no s_hist and no block barrier, no hist_open /
+// flush_hist, and p.hist a null constant wherever the window code tests it, so lane_fast_record and
+// frame_store carry no counting. That instance also drops amdgpu_num_sgpr(80): SGPRs do not limit
+// the occupancy of a 71-VGPR kernel on gfx950, and the cap only turned 39 SGPRs into v_writelane /
+// v_readlane pairs. Its dynamic LDS grows by the bytes of the s_hist it lacks, so both instances
+// allocate the same total per block and the resident blocks per CU do not change. Five interleaved
+// rounds against the parent (profiles/r10/ab_span_lean.log): 1M x 64 B 18.74-18.91 -> 18.39-18.63 us,
+// 4M 72.85-73.56 -> 72.13-72.97, 16M 279.9-282.7 -> 278.8-282.4. 0: every launch runs rx_lane_kernel.
+#ifndef HALO_RX_LANE_LEAN
+#define HALO_RX_LANE_LEAN 1
+#endif
+constexpr uint32_t kLaneHistLds = sizeof(uint32_t) * HALO_RX_STATUS_COUNT;
+constexpr uint32_t lane_dyn_lds(bool hist) { return HALO_RX_LANE_LDS_PAD + (hist ? 0u : kLaneHistLds); }
+
 template <int LAYOUT, int FUSE>
 __global__ void __launch_bounds__(HALO_RX_LANE_BLOCK) __attribute__((amdgpu_num_sgpr(80)))
 #if HALO_RX_LANE_WAVES
@@ -978,6 +1001,31 @@ rx_lane_kernel(const RxParams p) {
     flush_hist(p, hist);
 }
 
+// rx_lane_kernel for a launch without a histogram (HALO_RX_LANE_LEAN, above): the same windows
+// from the same waves. (The rejected knobs HALO_RX_LANE_XCD and _PREFETCH are not repeated here.)
+template <int LAYOUT, int FUSE>
+__global__ void __launch_bounds__(HALO_RX_LANE_BLOCK)
+#if HALO_RX_LANE_WAVES
+__attribute__((amdgpu_waves_per_eu(HALO_RX_LANE_WAVES)))
+#endif
+rx_lane_lean_kernel(const RxParams p_in) {
+    __shared__ uint4 s_rec[HALO_RX_LANE_BLOCK / 64][128];
+    RxParams p = p_in;
+    p.hist = nullptr;  // a constant for the window code: no counting is compiled in
+    Hist hist{nullptr, 0, 0};
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = threadIdx.x >> 6;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t base = wave * 64; base < p.n; base += nwaves * 64) {
+#if HALO_RX_LANE_FAST
+        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= HALO_RX_LANE_FAST_MAX_WAVES);
+#else
+        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist);
+#endif
+    }
+}
+
 // Several batches in one launch (halo_rx_parse_batches_device): the batch stream of the reference's
 // unbounded poll loop (engine/engine.go:344-351) handed over K batches at a time. A 1M-frame launch
 // spends a fixed ramp and tail filling and draining 256 CUs — config 2 ran at 0.62 of 8 TB/s while
@@ -997,13 +1045,20 @@ struct MultiParams {
     halo_rx_result_t* out[kMultiMax];
 };
 
-template <int LAYOUT>
+template <int LAYOUT, bool HIST = true>  // HIST false: the launch keeps no histogram (HALO_RX_LANE_LEAN)
 __global__ void __launch_bounds__(HALO_RX_LANE_BLOCK) rx_lane_multi_kernel(const MultiParams mp) {
     __shared__ uint32_t s_hist[HALO_RX_STATUS_COUNT];
     __shared__ uint4 s_rec[HALO_RX_LANE_BLOCK / 64][128];
-    if (threadIdx.x < HALO_RX_STATUS_COUNT) s_hist[threadIdx.x] = 0;
-    __syncthreads();
-    Hist hist = hist_open(mp.p, s_hist);
+    RxParams lean;
+    if constexpr (HIST) {
+        if (threadIdx.x < HALO_RX_STATUS_COUNT) s_hist[threadIdx.x] = 0;
+        __syncthreads();
+    } else {
+        lean = mp.p;
+        lean.hist = nullptr;
+    }
+    const RxParams& p0 = HIST ? mp.p : lean;
+    Hist hist = hist_open(p0, HIST ? s_hist : nullptr);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w = threadIdx.x >> 6;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1012,7 +1067,7 @@ __global__ void __launch_bounds__(HALO_RX_LANE_BLOCK) rx_lane_multi_kernel(const
     for (uint32_t win = wave; win < total; win += nwaves) {
         uint32_t b = 0;
         while (win >= mp.win_end[b]) ++b;  // k <= 32, uniform across the wave
-        RxParams p = mp.p;
+        RxParams p = p0;
         p.bytes = mp.bytes[b];
         p.offsets_dw = mp.offsets_dw[b];
         p.lens = mp.lens[b];
@@ -1025,7 +1080,18 @@ __global__ void __launch_bounds__(HALO_RX_LANE_BLOCK) rx_lane_multi_kernel(const
         lane_window<LAYOUT, 0, kStoreLane>(p, base, lane, s_rec[w], hist);
 #endif
     }
-    flush_hist(mp.p, hist);
+    if constexpr (HIST) flush_hist(p0, hist);
+}
+
+template <int LAYOUT>
+void launch_lane_multi(const MultiParams& mp, dim3 grid, hipStream_t s) {
+    if constexpr (HALO_RX_LANE_LEAN) {
+        if (!mp.p.hist) {
+            hipLaunchKernelGGL((rx_lane_multi_kernel<LAYOUT, false>), grid, dim3(HALO_RX_LANE_BLOCK), lane_dyn_lds(false), s, mp);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((rx_lane_multi_kernel<LAYOUT, true>), grid, dim3(HALO_RX_LANE_BLOCK), lane_dyn_lds(true), s, mp);
 }
 
 // The resident small-poll consumer (RingServiceCtl, halo_common.h), kSvcGroups workgroups of
@@ -1678,8 +1744,15 @@ hipError_t launch_variant(const RxParams& p, int variant, hipStream_t s) {
             // each: half the arrivals in the histogram tree, whose tail is a fixed cost per launch
             // (1M x 64 B: +2.1 instead of +2.7 us, 8192 blocks; 4096 gave no gain, profiles/r05/r5zm)
             if (p.hist && grid <= HALO_RX_HIST_HALVE_MAX) grid = (grid + 1) / 2;
+            if constexpr (HALO_RX_LANE_LEAN) {
+                if (!p.hist) {
+                    hipLaunchKernelGGL((rx_lane_lean_kernel<LAYOUT, FUSE>), dim3(grid),
+                                       dim3(HALO_RX_LANE_BLOCK), lane_dyn_lds(false), s, p);
+                    break;
+                }
+            }
             hipLaunchKernelGGL((rx_lane_kernel<LAYOUT, FUSE>), dim3(grid),
-                               dim3(HALO_RX_LANE_BLOCK), HALO_RX_LANE_LDS_PAD, s, p);
+                               dim3(HALO_RX_LANE_BLOCK), lane_dyn_lds(true), s, p);
             break;
         }
         case kVariantStream: {
@@ -2042,9 +2115,9 @@ extern "C" HALO_API int halo_rx_parse_batches_device(const halo_rx_batch_desc_t*
     constexpr uint32_t wpb = HALO_RX_LANE_BLOCK / 64;
     const dim3 grid(halo::grid_for(windows * 64u, 64, HALO_RX_LANE_MAX_BLOCKS * 4 / wpb, wpb));
     if (flags & HALO_RX_L3_START)
-        hipLaunchKernelGGL(halo::rx_lane_multi_kernel<3>, grid, dim3(HALO_RX_LANE_BLOCK), HALO_RX_LANE_LDS_PAD, s, mp);
+        halo::launch_lane_multi<3>(mp, grid, s);
     else
-        hipLaunchKernelGGL(halo::rx_lane_multi_kernel<0>, grid, dim3(HALO_RX_LANE_BLOCK), HALO_RX_LANE_LDS_PAD, s, mp);
+        halo::launch_lane_multi<0>(mp, grid, s);
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }
 

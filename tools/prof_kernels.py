@@ -41,6 +41,8 @@ WORKLOADS = [
     # each): the same bytes in and out with no build work, for counters next to the build's
     ("probe_tx_build_64B", dict(length=64), 1 << 20, 1, 10, 0, 1, 22),
     ("probe_tx_build_1514B", dict(length=64), 1 << 18, 1, 10, 0, 1, 1472),
+    # config 2's size-matched probe: its frames, offsets and lengths in, its records out
+    ("probe_config2", dict(length=64), 1 << 20, 8, 10, 0, 1, 64),
 ]
 
 
@@ -107,6 +109,12 @@ def main():
             torch.cuda.synchronize()
             print(f"{name}: {launches} launches of {n}", flush=True)
             del bs, out, pk
+            torch.cuda.empty_cache()
+            continue
+        if name == "probe_config2":
+            del bs, out
+            k = bench.size_matched_probe(dev, n * (64 + 6), n * 32, bench.Dist(), nbuf=rot, steps=launches)
+            print(f"{name}: {launches} launches per shape, {bench.LAST_PROBE_SHAPES} (best {k:.5f} ms)", flush=True)
             torch.cuda.empty_cache()
             continue
         if name.startswith("probe_tx_build"):
