@@ -142,6 +142,19 @@ ARP_V = {name: code for code, name in enumerate(ARP_VERDICT_NAMES)}
 ARP_V_COUNT = len(ARP_VERDICT_NAMES)
 ARP_MAX_NETIFS = 64
 ARP_AGE, ARP_REFRESH_AHEAD = 300, 10
+# port-mapping return flows: halo_pmflow_item_t (20 bytes), halo_pmflow_entry_t (24), halo_pmflow_via_t (8),
+# halo_pmflow_layout_stats_t, HALO_PMFLOW_V_*
+PMFLOW_ITEM_DTYPE = np.dtype([("index", "<u4"), ("remote_ip", "<u4"), ("lan_ip", "<u4"), ("remote_port", "<u2"),
+                              ("lan_port", "<u2"), ("wan_port", "<u2"), ("proto", "u1"), ("pad", "u1")])
+PMFLOW_ENTRY_DTYPE = np.dtype([("remote_ip", "<u4"), ("lan_ip", "<u4"), ("last_alive", "<u4"), ("id", "<u4"),
+                               ("remote_port", "<u2"), ("lan_port", "<u2"), ("wan_port", "<u2"), ("proto", "u1"),
+                               ("wan_netif", "u1")])
+PMFLOW_VIA_DTYPE = np.dtype([("verdict", "u1"), ("wan_netif", "u1"), ("wan_port", "<u2"), ("next_hop", "<u4")])
+assert PMFLOW_ITEM_DTYPE.itemsize == 20 and PMFLOW_ENTRY_DTYPE.itemsize == 24 and PMFLOW_VIA_DTYPE.itemsize == 8
+PMFLOW_LAYOUT_DTYPE = np.dtype([("slots", "<u4"), ("entries", "<u4"), ("longest_chain", "<u4"), ("wrapped", "<u4")])
+PMFLOW_VERDICT_NAMES = ("NONE", "MISS", "HIT", "OVERRIDE")
+PMFLOW_V = {name: code for code, name in enumerate(PMFLOW_VERDICT_NAMES)}
+PMFLOW_V_COUNT = len(PMFLOW_VERDICT_NAMES)
 # the egress step: halo_egress_port_t (24 bytes), HALO_EGRESS_KIND_*
 EGRESS_PORT_DTYPE = np.dtype([("frames", "<u4"), ("frames_written", "<u4"), ("bytes", "<u8"), ("bytes_written", "<u8")])
 assert EGRESS_PORT_DTYPE.itemsize == 24
@@ -274,6 +287,13 @@ class ArpConfig(ctypes.Structure):
 
     _fields_ = [("n_netifs", ctypes.c_uint32), ("netif", NetIf * 64), ("capacity", ctypes.c_uint32),
                 ("slots_log2", ctypes.c_uint32)]
+
+
+class PmflowConfig(ctypes.Structure):
+    """halo_pmflow_config_t."""
+
+    _fields_ = [("n_netifs", ctypes.c_uint32), ("netif", NetIf * 64), ("gateway", ctypes.c_uint32 * 64),
+                ("capacity", ctypes.c_uint32), ("capacity_log2", ctypes.c_uint32)]
 
 
 class EgressConfig(ctypes.Structure):
@@ -453,6 +473,28 @@ _PROTOS = {
         _u8p]),
     "halo_arp_encap_tx_device": (ctypes.c_int, [
         ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p,
+        ctypes.c_void_p]),
+    "halo_pmflow_table_create": (ctypes.c_int, [ctypes.POINTER(PmflowConfig), ctypes.POINTER(ctypes.c_void_p)]),
+    "halo_pmflow_table_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "halo_pmflow_record": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_pmflow_get": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint16, ctypes.c_uint32, ctypes.c_uint16, ctypes.c_uint8,
+        ctypes.POINTER(ctypes.c_uint32), _u8p, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_pmflow_expire": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_pmflow_list": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_pmflow_layout_stats": (ctypes.c_int, [ctypes.c_void_p, _u8p]),
+    "halo_pmflow_dirty": (ctypes.c_int, [ctypes.c_void_p]),
+    "halo_pmflow_sync_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "halo_pmflow_lookup_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_void_p]),
+    "halo_pmflow_record_workspace": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "halo_pmflow_record_device": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p,
+        ctypes.c_uint32, _u8p, _u8p, ctypes.c_uint64, ctypes.c_void_p]),
+    "halo_arp_drop_device": (ctypes.c_int, [_u8p, _u8p, ctypes.c_uint32, ctypes.c_void_p]),
+    "halo_arp_encap_via_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p,
         ctypes.c_void_p]),
     "halo_tx_respond_workspace": (ctypes.c_uint64, [ctypes.c_uint32]),
     "halo_tx_respond_device": (ctypes.c_int, [

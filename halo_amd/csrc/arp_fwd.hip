@@ -1,8 +1,9 @@
 // arp_fwd.hip — the device side of the ARP neighbour cache (arp_table.cc is its host control
 // plane) on gfx950: the bare GetArpCache over a batch of (netif, ip) pairs, the forward path's L2
 // step (engine/ipv4_engine.go:180-201, :226-236, :267: route id -> next hop -> GetArpCache -> the
-// Ethernet header BuildEthFrm writes) over a device-resident batch, and the gather that brings a
-// parsed batch's ARP messages to the host in frame order.
+// Ethernet header BuildEthFrm writes) over a device-resident batch — also with the out-interface
+// override of a port-mapping return flow (:180-186, halo_arp_encap_via_device; pmflow_fwd.hip makes
+// the via array) — and the gather that brings a parsed batch's ARP messages to the host in frame order.
 //
 // Layout: a power-of-two array of 16-byte slots {ip, used | netif, mac[0..3], mac[4..5]} placed by
 // linear probing from key_hash(netif, ip) & mask, the hash the host compile shares. A probe is one
@@ -114,12 +115,17 @@ __global__ void __launch_bounds__(256) arp_lookup_kernel(const ArpView v, const 
 // (engine/ipv4_engine.go:50-99) for frames NetIf in_arg originated: a x.x.x.255 destination goes
 // out of that NetIf to the broadcast MAC without a route, and dst == the out NetIf's address is a
 // LOOPBACK whatever nat_enable says. The forward instantiation holds none of the Tx branches.
-template <bool kTx>
-__global__ void __launch_bounds__(256) arp_encap_kernel(const ArpView v, uint8_t* bytes, const uint32_t* __restrict__ offsets_dw,
-                                                        const uint16_t* __restrict__ lens, uint32_t n,
-                                                        const uint32_t* __restrict__ route_ids, uint32_t in_arg,
-                                                        const uint8_t* __restrict__ select, uint2* __restrict__ results,
-                                                        uint32_t* counts, uint32_t* miss_count) {
+//
+// kVia: the return-flow override of :180-186 (halo_arp_encap_via_device). Where via[i] says
+// OVERRIDE, (next hop, out NetIf) come from it and the route id is not consulted; everything from
+// the LOOPBACK test on is the same code. The body is shared and inlined into each kernel, so the
+// instantiations without kVia compile to what they were.
+template <bool kTx, bool kVia>
+__device__ __forceinline__ void arp_encap_body(const ArpView& v, uint8_t* bytes, const uint32_t* __restrict__ offsets_dw,
+                                               const uint16_t* __restrict__ lens, uint32_t n,
+                                               const uint32_t* __restrict__ route_ids, uint32_t in_arg,
+                                               const uint8_t* __restrict__ select, const uint2* __restrict__ via,
+                                               uint2* __restrict__ results, uint32_t* counts, uint32_t* miss_count) {
     __shared__ uint32_t s_counts[HALO_ARP_V_COUNT];
     if (threadIdx.x < HALO_ARP_V_COUNT) s_counts[threadIdx.x] = 0;
     __syncthreads();
@@ -132,14 +138,29 @@ __global__ void __launch_bounds__(256) arp_encap_kernel(const ArpView v, uint8_t
             uint32_t out = 0xFFu, tx = 0, target = 0;
             // the loads that depend on nothing but i go out together, then the frame's and the
             // route's side by side: the chain is index arrays -> {frame, route -> NetIf} -> slot
-            const uint32_t len = lens[i], off = offsets_dw[i], rid = route_ids[i];
+            const uint32_t len = lens[i], off = offsets_dw[i];
+            uint32_t rid = route_ids[i];
             const bool sel = !select || select[i];
+            uint2 r = make_uint2(0u, 0xFFFFFFFFu);
+            bool routed;
+            if (kVia) {
+                // the route word is loaded whatever the via says, so that the two loads go out
+                // together and the chain to the slot is no longer than without a via
+                const uint2 w = via[i];  // verdict | wan_netif << 8 | wan_port << 16; next_hop
+                routed = rid < v.n_routes;
+                if (routed) r = *reinterpret_cast<const uint2*>(v.routes + rid);
+                if ((w.x & 0xFFu) == HALO_PMFLOW_V_OVERRIDE) {
+                    r = make_uint2(w.y, (w.x >> 8) & 0xFFu);
+                    rid = 0;  // neither NONE nor PANIC: the forced pair stands for the route
+                    routed = true;
+                }
+            }
             if (sel && len >= 34u) {
                 uint8_t* f = bytes + 4ull * off;
                 uint32_t* p = reinterpret_cast<uint32_t*>(f);
-                const bool routed = rid < v.n_routes;
+                if (!kVia) routed = rid < v.n_routes;
                 const uint32_t w3 = p[3], w7 = p[7], h = *reinterpret_cast<const uint16_t*>(f + 32);
-                const uint2 r = routed ? *reinterpret_cast<const uint2*>(v.routes + rid) : make_uint2(0u, 0xFFFFFFFFu);
+                if (!kVia) r = routed ? *reinterpret_cast<const uint2*>(v.routes + rid) : make_uint2(0u, 0xFFFFFFFFu);
                 if ((w3 & 0xFFFFu) != 0x0008u) {  // bytes 12-13 are not 08 00
                 } else if (kTx && (h >> 8) == 255u) {  // :60-61, :85-86: no FindRoute, no GetArpCache
                     out = in_arg;
@@ -191,6 +212,26 @@ __global__ void __launch_bounds__(256) arp_encap_kernel(const ArpView v, uint8_t
         if (counts) atomicAdd(counts + threadIdx.x, s_counts[threadIdx.x]);
         if (threadIdx.x == HALO_ARP_V_MISS) atomicAdd(miss_count, s_counts[threadIdx.x]);
     }
+}
+
+template <bool kTx>
+__global__ void __launch_bounds__(256) arp_encap_kernel(const ArpView v, uint8_t* bytes, const uint32_t* __restrict__ offsets_dw,
+                                                        const uint16_t* __restrict__ lens, uint32_t n,
+                                                        const uint32_t* __restrict__ route_ids, uint32_t in_arg,
+                                                        const uint8_t* __restrict__ select, uint2* __restrict__ results,
+                                                        uint32_t* counts, uint32_t* miss_count) {
+    arp_encap_body<kTx, false>(v, bytes, offsets_dw, lens, n, route_ids, in_arg, select, nullptr, results, counts,
+                               miss_count);
+}
+
+__global__ void __launch_bounds__(256) arp_encap_via_kernel(const ArpView v, uint8_t* bytes,
+                                                            const uint32_t* __restrict__ offsets_dw,
+                                                            const uint16_t* __restrict__ lens, uint32_t n,
+                                                            const uint32_t* __restrict__ route_ids, uint32_t in_arg,
+                                                            const uint8_t* __restrict__ select, const uint2* __restrict__ via,
+                                                            uint2* __restrict__ results, uint32_t* counts,
+                                                            uint32_t* miss_count) {
+    arp_encap_body<false, true>(v, bytes, offsets_dw, lens, n, route_ids, in_arg, select, via, results, counts, miss_count);
 }
 
 // halo_rx_dispatch's HALO_RX_ACT_ARP: status OK, EtherType 0x0806, MAC_MATCH (the record's first dword)
@@ -447,8 +488,9 @@ int ops_lookup(const halo_arp_table* t, const uint32_t* d_ips, const uint8_t* d_
 }
 
 int ops_encap(const halo_arp_table* t, uint8_t* d_bytes, const uint32_t* d_offsets_dw, const uint16_t* d_lens, uint32_t n,
-              const uint32_t* d_route_ids, uint32_t in_netif, bool tx, const uint8_t* d_select, halo_arp_result_t* d_results,
-              uint32_t* d_counts, uint32_t* d_miss_count, halo_stream_t stream) {
+              const uint32_t* d_route_ids, uint32_t in_netif, bool tx, const uint8_t* d_select,
+              const halo_pmflow_via_t* d_via, halo_arp_result_t* d_results, uint32_t* d_counts, uint32_t* d_miss_count,
+              halo_stream_t stream) {
     ArpDevice* d = dev_of(t);
     if (!d) return HALO_E_INVAL;  // never synced
     std::shared_lock<std::shared_mutex> lk(d->view_mu);
@@ -462,9 +504,15 @@ int ops_encap(const halo_arp_table* t, uint8_t* d_bytes, const uint32_t* d_offse
          reinterpret_cast<uintptr_t>(d_miss_count)) & 3u)
         return HALO_E_INVAL;
     if ((reinterpret_cast<uintptr_t>(d_lens) & 1u) || (reinterpret_cast<uintptr_t>(d_results) & 7u)) return HALO_E_INVAL;
+    if (reinterpret_cast<uintptr_t>(d_via) & 7u) return HALO_E_INVAL;
     const int rc = check_device();
     if (rc) return rc;
-    if (tx)
+    if (d_via)  // forward path only; without it the plain forward kernel is the same computation
+        hipLaunchKernelGGL(arp_encap_via_kernel, dim3(arp_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), v,
+                           d_bytes, d_offsets_dw, d_lens, n, d_route_ids, t->cfg.netif[in_netif].nat_enable ? 1u : 0u,
+                           d_select, reinterpret_cast<const uint2*>(d_via), reinterpret_cast<uint2*>(d_results), d_counts,
+                           d_miss_count);
+    else if (tx)
         hipLaunchKernelGGL(arp_encap_kernel<true>, dim3(arp_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), v,
                            d_bytes, d_offsets_dw, d_lens, n, d_route_ids, in_netif, d_select,
                            reinterpret_cast<uint2*>(d_results), d_counts, d_miss_count);

@@ -289,8 +289,8 @@ extern "C" HALO_API int halo_arp_encap_device(const halo_arp_table_t* t, uint8_t
     if (!t) return HALO_E_INVAL;
     if (in_netif >= t->cfg.n_netifs) return HALO_E_RANGE;
     const DeviceOps* ops = device_ops ? device_ops() : nullptr;
-    return ops ? ops->encap(t, d_bytes, d_offsets_dw, d_lens, n, d_route_ids, in_netif, false, d_select, d_results,
-                            d_counts, d_miss_count, stream)
+    return ops ? ops->encap(t, d_bytes, d_offsets_dw, d_lens, n, d_route_ids, in_netif, false, d_select, nullptr,
+                            d_results, d_counts, d_miss_count, stream)
                : HALO_E_NODEV;
 }
 
@@ -301,8 +301,21 @@ extern "C" HALO_API int halo_arp_encap_tx_device(const halo_arp_table_t* t, uint
     if (!t) return HALO_E_INVAL;
     if (self_netif >= t->cfg.n_netifs) return HALO_E_RANGE;
     const DeviceOps* ops = device_ops ? device_ops() : nullptr;
-    return ops ? ops->encap(t, d_bytes, d_offsets_dw, d_lens, n, d_route_ids, self_netif, true, d_select, d_results,
-                            d_counts, d_miss_count, stream)
+    return ops ? ops->encap(t, d_bytes, d_offsets_dw, d_lens, n, d_route_ids, self_netif, true, d_select, nullptr,
+                            d_results, d_counts, d_miss_count, stream)
+               : HALO_E_NODEV;
+}
+
+extern "C" HALO_API int halo_arp_encap_via_device(const halo_arp_table_t* t, uint8_t* d_bytes, const uint32_t* d_offsets_dw,
+                                                  const uint16_t* d_lens, uint32_t n, const uint32_t* d_route_ids,
+                                                  uint32_t in_netif, const uint8_t* d_select,
+                                                  const halo_pmflow_via_t* d_via, halo_arp_result_t* d_results,
+                                                  uint32_t* d_counts, uint32_t* d_miss_count, halo_stream_t stream) {
+    if (!t) return HALO_E_INVAL;
+    if (in_netif >= t->cfg.n_netifs) return HALO_E_RANGE;
+    const DeviceOps* ops = device_ops ? device_ops() : nullptr;
+    return ops ? ops->encap(t, d_bytes, d_offsets_dw, d_lens, n, d_route_ids, in_netif, false, d_select, d_via,
+                            d_results, d_counts, d_miss_count, stream)
                : HALO_E_NODEV;
 }
 

@@ -83,6 +83,7 @@ struct DeviceOps {
                   uint8_t* d_mac8, uint8_t* d_verdict, uint32_t* d_miss_count, halo_stream_t stream);
     int (*encap)(const halo_arp_table* t, uint8_t* d_bytes, const uint32_t* d_offsets_dw, const uint16_t* d_lens, uint32_t n,
                  const uint32_t* d_route_ids, uint32_t in_netif, bool tx, const uint8_t* d_select,
+                 const halo_pmflow_via_t* d_via,  // forward path only (tx = false); null: no override
                  halo_arp_result_t* d_results, uint32_t* d_counts, uint32_t* d_miss_count, halo_stream_t stream);
     int (*gather)(const uint8_t* d_bytes, const uint32_t* d_offsets_dw, const uint16_t* d_lens,
                   const halo_rx_result_t* d_records, uint32_t n, uint32_t netif, halo_arp_msg_t* d_msgs, uint32_t cap,

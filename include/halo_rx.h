@@ -697,9 +697,9 @@ HALO_API int halo_rx_parse_route_batch_device(const uint8_t* d_bytes, const uint
  * IcmpTtlDeepNat (engine/icmp_engine.go:55-86) run on the GPU over the parsed records, writing the
  * halo_tx_op_t array halo_tx_fixup_batch_device consumes. Only new flows (device MISS) take the
  * host slow path, halo_nat_resolve_misses. One table per NATing NetIf. All addresses are in
- * IpAddrToU form. Not covered: the router-global NatPortMappingFlowTable (:160-186, :238-266),
- * which stays the caller's. The ARP step that follows the rewrite is halo_arp_encap_device ("ARP
- * neighbour cache" below).
+ * IpAddrToU form. The router-global NatPortMappingFlowTable (:160-186, :238-266) is its own
+ * table ("port-mapping return flows" below). The ARP step that follows the rewrite is
+ * halo_arp_encap_device ("ARP neighbour cache" below).
  *
  * Flow ids identify NatFlow objects: each NatAddFlow gets a fresh id, never reused, so that an id
  * read from a device table that is one generation old still names the same flow. LastAliveTime
@@ -972,7 +972,7 @@ HALO_API int halo_switch_debug_set_epoch(halo_switch_t* sw, uint32_t epoch);
  * below) writes the padded copy and the per-port index lists.
  * Locally originated packets take TxIpv4's variant of the step, halo_arp_encap_tx_device, on the
  * frames halo_tx_build_batch_device built ("local responders" below).
- * Not covered: Router.Ipv4PktFwdHook; NatPortMappingFlowTable; compact records in the gather; DHCP;
+ * Not covered: Router.Ipv4PktFwdHook; compact records in the gather; DHCP;
  * UDP service replies (the handlers' job); sending the LoChan copy of a LOOPBACK. */
 typedef struct halo_arp_table halo_arp_table_t;
 #define HALO_ARP_MAX_NETIFS 64u
@@ -1133,6 +1133,185 @@ HALO_API int halo_arp_gather_device(const uint8_t* d_bytes, const uint32_t* d_of
                                     const halo_rx_result_t* d_records, uint32_t n, uint32_t netif,
                                     halo_arp_msg_t* d_msgs, uint32_t cap, uint32_t* d_count, void* d_workspace,
                                     uint64_t workspace_bytes, halo_stream_t stream);
+
+/* ---- port-mapping return flows: source-in, source-out -----------------------------------------
+ * The Router's NatPortMappingFlowTable (engine/ipv4_engine.go:160-186, :203-207, :238-266,
+ * :489-516): what sends the replies of a statically port-forwarded connection back out of the WAN
+ * NetIf the connection came in on, with that NetIf's address and the mapping's WAN port as source.
+ * One table per Router. The host table is the control plane and the authority; halo_pmflow_sync_device
+ * compiles it into an open-addressing table in HBM and the two per-packet halves run on the GPU:
+ *
+ *   reference                                      here
+ *   :160-179  Get(reversed 5-tuple) on a non-NAT   halo_pmflow_lookup_device over the records the
+ *             in-NetIf, LastAliveTime = TimeNow    LAN-side NetIf received (host: halo_pmflow_get)
+ *   :180-186  out NetIf / next hop forced to the   d_via[i] = OVERRIDE, consumed by
+ *             flow's WanNetIf and its Gateway      halo_arp_encap_via_device
+ *   :203-207  NatChangeSrc(outNetIf.IpAddr,        ops[i]: HALO_TX_NAT_SRC, src_ip, src_port; d_hit[i]
+ *             flow.WanPort) ahead of the           = 1 is the d_skip of the out NetIf's
+ *             out-NetIf's own mapping / flow       halo_nat_lookup_lan_device
+ *   :238-266  Get / MallocType / Set after route   halo_pmflow_record_device lists the frames after
+ *             and ARP succeeded; full -> return    halo_arp_encap_device; halo_pmflow_record applies
+ *             before TxEthernet                    them in frame order; dropped_out ->
+ *                                                  halo_arp_drop_device
+ *   :497-516  NatPortMappingFlowClear              halo_pmflow_expire
+ *
+ * KEY: the whole 13-byte NatFlowHash {remote_ip, remote_port, lan_ip, lan_port, proto}, compared
+ * whole, normalised by no NAT type. VALUE: {wan_netif (an index, as everywhere here), wan_port,
+ * last_alive, id}; ids are fresh per insert and never reused, and LastAliveTime lives on the device
+ * as one u32 per id shared by both generations, exactly as the NAT flow table's does (above).
+ * Only TCP and UDP flows can exist: the record is made for a NatPortMappingEntry, and
+ * CheckNatPortMapping (:683-707) matches no other protocol. halo_pmflow_record therefore refuses an
+ * item of another protocol (HALO_E_INVAL), and the device lookup answers such a record (ICMP, ...)
+ * MISS without a probe.
+ * STAMPING: the reference stamps only packets that passed the TTL step (:133-142). Records carry
+ * no TTL, so a caller that does not deselect dead packets (d_select) stamps for them too — the
+ * convention the NAT lookups already have.
+ * ORDERING: device lookups see the table as of the last halo_pmflow_sync_device (or the last
+ * halo_pmflow_expire that removed a flow). A flow recorded since is a device MISS for the lookup
+ * (halo_pmflow_get on the host answers for it) and is listed again by halo_pmflow_record_device,
+ * where halo_pmflow_record overwrites it identically: results do not depend on the sync cadence.
+ * FAILURE: argument errors (HALO_E_INVAL / _RANGE) leave the table as it was and are checked before
+ * a device is looked for. A library built without the device side answers HALO_E_NODEV to the
+ * *_device calls. Not covered: Router.Ipv4PktFwdHook; DHCP; device-side inserts (order and the
+ * capacity check depend on frame order, as NatAddFlow's do); interface names. */
+typedef struct halo_pmflow_table halo_pmflow_table_t;
+typedef struct halo_pmflow_config {
+    uint32_t n_netifs;                          /* 1..64                                               */
+    halo_rx_netif_t netif[HALO_ARP_MAX_NETIFS]; /* NetIfs 0..n_netifs-1: ip and nat_enable are read    */
+    uint32_t gateway[HALO_ARP_MAX_NETIFS];      /* IpAddrToU(NetIf.Gateway); 0 for nil                 */
+    uint32_t capacity;                          /* most flows (the StaticAllocator's room); > 0        */
+    uint32_t capacity_log2;                     /* 0: automatic (load <= 0.5); else the device table has
+                                                   exactly 2^capacity_log2 slots (<= 28; tests). A table
+                                                   that does not fit (entries >= slots) makes sync /
+                                                   layout_stats return HALO_E_RANGE                     */
+} halo_pmflow_config_t;
+typedef struct halo_pmflow_item { /* one frame to record, as halo_pmflow_record_device writes it */
+    uint32_t index;       /* the frame's index in its batch                  */
+    uint32_t remote_ip;   /* the frame's source address                      */
+    uint32_t lan_ip;      /* NatPortMappingEntry.LanHostIpAddr               */
+    uint16_t remote_port; /* the frame's source port                         */
+    uint16_t lan_port;    /* NatPortMappingEntry.LanHostPort                 */
+    uint16_t wan_port;    /* NatPortMappingEntry.WanPort                     */
+    uint8_t proto;        /* 6 or 17                                         */
+    uint8_t pad;
+} halo_pmflow_item_t;     /* 20 B */
+typedef struct halo_pmflow_entry { /* a NatPortMappingFlow with its key */
+    uint32_t remote_ip;
+    uint32_t lan_ip;
+    uint32_t last_alive; /* LastAliveTime (host copy; device stamps are folded in by expire / sync) */
+    uint32_t id;
+    uint16_t remote_port;
+    uint16_t lan_port;
+    uint16_t wan_port;   /* WanPort  */
+    uint8_t proto;
+    uint8_t wan_netif;   /* WanNetIf */
+} halo_pmflow_entry_t;   /* 24 B */
+#define HALO_PMFLOW_V_NONE 0u     /* ip_proto == 0xFF or not selected: nothing looked up                */
+#define HALO_PMFLOW_V_MISS 1u     /* no flow: the route and the out NetIf's own NAT lookup decide        */
+#define HALO_PMFLOW_V_HIT 2u      /* a flow, and the route already points at its WAN NetIf (or the route
+                                     id is HALO_ROUTE_PANIC, which the encap reports)                    */
+#define HALO_PMFLOW_V_OVERRIDE 3u /* a flow, and the route names another NetIf, none (HALO_ROUTE_NONE:
+                                     an empty outNetIfName differs from any WanNetIf, :182) or an id the
+                                     device copy does not know: (out NetIf, next hop) are forced          */
+#define HALO_PMFLOW_V_COUNT 4u
+typedef struct halo_pmflow_via {
+    uint8_t verdict;    /* HALO_PMFLOW_V_*                                   */
+    uint8_t wan_netif;  /* HIT, OVERRIDE: the flow's WanNetIf; else 0xFF     */
+    uint16_t wan_port;  /* HIT, OVERRIDE: the flow's WanPort; else 0         */
+    uint32_t next_hop;  /* HIT, OVERRIDE: gateway[wan_netif]; else 0         */
+} halo_pmflow_via_t;    /* 8 B */
+typedef struct halo_pmflow_layout_stats {
+    uint32_t slots;
+    uint32_t entries;
+    uint32_t longest_chain; /* most slots any entry's lookup reads (1 = at its home slot) */
+    uint32_t wrapped;       /* entries whose probe chain runs past the last slot to slot 0 */
+} halo_pmflow_layout_stats_t;
+
+/* HALO_E_INVAL: null pointer, n_netifs outside 1..64, capacity 0; HALO_E_RANGE: capacity_log2 > 28. */
+HALO_API int halo_pmflow_table_create(const halo_pmflow_config_t* cfg, halo_pmflow_table_t** out);
+HALO_API int halo_pmflow_table_destroy(halo_pmflow_table_t* t);
+/* :238-266 for items[0..k) in ascending order, frames NetIf `in_netif` received, at time `now`.
+ * An absent key is inserted unless the table holds `capacity` flows: then dropped_out[j] = 1 (the
+ * reference returns before TxEthernet: the frame is not sent) and nothing is stored. A present key
+ * always has wan_netif = in_netif, wan_port and last_alive overwritten, also when the table is full.
+ * dropped_out[j] = 0 otherwise. *n_added (optional) = the inserts. HALO_E_RANGE: in_netif >=
+ * n_netifs. HALO_E_INVAL, nothing applied: a null array with k > 0, an item whose proto is not 6 or 17. */
+HALO_API int halo_pmflow_record(halo_pmflow_table_t* t, uint32_t in_netif, const halo_pmflow_item_t* items,
+                                uint32_t k, uint32_t now, uint8_t* dropped_out, uint32_t* n_added);
+/* The host lookup of :164-179: *found = 1 and *out (optional) = the flow, or *found = 0. When
+ * now_or_no_stamp is not NULL a found flow's LastAliveTime = *now_or_no_stamp (:176), and *out
+ * shows it. */
+HALO_API int halo_pmflow_get(halo_pmflow_table_t* t, uint32_t remote_ip, uint16_t remote_port, uint32_t lan_ip,
+                             uint16_t lan_port, uint8_t proto, const uint32_t* now_or_no_stamp,
+                             halo_pmflow_entry_t* out, uint32_t* found);
+/* One NatPortMappingFlowClear tick (:497-516): every flow with (uint32_t)(now - LastAliveTime) > 60
+ * leaves. The stamps the device wrote are folded in first, the later in serial-number order as
+ * halo_nat_expire does, so THE CALLER MUST HAVE SYNCHRONISED THE STREAMS ITS LOOKUPS RAN ON. When
+ * flows were removed and a device copy exists, it is rebuilt and published before the call returns. */
+HALO_API int halo_pmflow_expire(halo_pmflow_table_t* t, uint32_t now, uint32_t* n_removed);
+/* Up to `cap` flows in ascending id (NULL with cap 0 to count), *n = the total. */
+HALO_API int halo_pmflow_list(const halo_pmflow_table_t* t, halo_pmflow_entry_t* out, uint32_t cap, uint32_t* n);
+/* The layout halo_pmflow_sync_device would upload now. Host only. */
+HALO_API int halo_pmflow_layout_stats(const halo_pmflow_table_t* t, halo_pmflow_layout_stats_t* out);
+/* 1 when the host table differs from the published device copy (or none exists): an insert, a
+ * changed wan_netif / wan_port or a removal since. A refreshed LastAliveTime alone does not count. */
+HALO_API int halo_pmflow_dirty(const halo_pmflow_table_t* t);
+/* Compile the table into HBM on `device` and publish it (synchronous): 32-byte slots {remote ip,
+ * lan ip, remote port | lan port << 16, used | proto; wan_netif, wan_port, id, pad} placed by linear
+ * probing from XXH3-64(key) & (slots - 1), the hash of halo_flow_hash_device; the NetIf {ip,
+ * nat_enable, gateway} array; and, when `routes` is not NULL, the NetIf of every route id, read
+ * through halo_route_get as halo_arp_sync_device reads it. Two generations under
+ * halo_nat_sync_device's discipline (drain, fold the stamps, rewrite the unused generation,
+ * release-publish; a lookup holds the read lock until its kernel is enqueued). One device per table. */
+HALO_API int halo_pmflow_sync_device(halo_pmflow_table_t* t, const halo_route_table_t* routes, int device);
+/* The LAN-side half (:160-186, :203-207) for the records a non-NAT NetIf received, given the route
+ * id FindRoute returned for each. Key: remote = dst_ip : dport, LAN host = src_ip : sport, ip_proto.
+ *   ip_proto == 0xFF, or d_select && d_select[i] == 0 -> NONE
+ *   ip_proto not 6 / 17, or no such flow              -> MISS
+ *   a flow -> its stamp = now (plain store), then HIT / OVERRIDE as defined above; if
+ *     netif[wan_netif].nat_enable: ops[i].steps |= HALO_TX_NAT_SRC, src_ip = netif[wan_netif].ip,
+ *     src_port = wan_port. No other op field is written, and no op of a NONE or MISS record.
+ * d_via[i] (8-byte aligned) and d_hit[i] (1 on HIT / OVERRIDE, else 0: the d_skip of the out NetIf's
+ * halo_nat_lookup_lan_device) are written for every record. d_counts (optional):
+ * HALO_PMFLOW_V_COUNT u32 counters, INCREMENTED. Records and ops 16-byte aligned; route ids and
+ * counts 4. HALO_E_INVAL before the first sync and when the last sync had routes == NULL. n == 0
+ * is OK. Asynchronous on `stream`. */
+HALO_API int halo_pmflow_lookup_device(const halo_pmflow_table_t* t, const halo_rx_result_t* d_records, uint32_t n,
+                                       uint32_t now, const uint32_t* d_route_ids, const uint8_t* d_select,
+                                       halo_tx_op_t* d_ops, halo_pmflow_via_t* d_via, uint8_t* d_hit,
+                                       uint32_t* d_counts, halo_stream_t stream);
+/* The WAN-side half (:238-266) for the frames NATing NetIf `in_netif` received, after
+ * halo_arp_encap_device in stream order. Frame i is a candidate when d_wan_verdict[i] ==
+ * HALO_NAT_V_MAPPING and d_arp_results[i].verdict == HALO_ARP_V_HIT; its key is remote = the record's
+ * src_ip : sport, LAN host = ops[i].dst_ip : dst_port, the record's ip_proto; wan_port = the record's
+ * dport. A candidate the device copy holds with the same (wan_netif = in_netif, wan_port) is only
+ * stamped with `now`; every other candidate is written densely to d_items (4-byte aligned) in
+ * ascending frame index, for halo_pmflow_record. *d_count is SET to the number listed, also beyond
+ * `cap`; only the first `cap` are written. d_workspace: halo_pmflow_record_workspace(n) bytes, 4-byte
+ * aligned; one workspace serves any number of calls on one stream. Three launches (count, scan,
+ * scatter). HALO_E_INVAL before the first sync; HALO_E_RANGE: in_netif >= n_netifs. */
+HALO_API uint64_t halo_pmflow_record_workspace(uint32_t n);
+HALO_API int halo_pmflow_record_device(const halo_pmflow_table_t* t, uint32_t in_netif,
+                                       const halo_rx_result_t* d_records, const uint8_t* d_wan_verdict,
+                                       const halo_tx_op_t* d_ops, const halo_arp_result_t* d_arp_results, uint32_t n,
+                                       uint32_t now, halo_pmflow_item_t* d_items, uint32_t cap, uint32_t* d_count,
+                                       void* d_workspace, uint64_t workspace_bytes, halo_stream_t stream);
+/* For the frames halo_pmflow_record dropped: d_results[d_index[j]] = {HALO_ARP_V_NONE, 0xFF, 0, 0}
+ * for j < k, so that halo_tx_egress_arp_device leaves them out. Bytes 0-11 of such a frame were
+ * already rewritten by the encap and stay so. Every d_index[j] must be below the batch size. */
+HALO_API int halo_arp_drop_device(halo_arp_result_t* d_results, const uint32_t* d_index, uint32_t k,
+                                  halo_stream_t stream);
+/* halo_arp_encap_device with the return-flow override (:180-186). Where d_via[i].verdict ==
+ * HALO_PMFLOW_V_OVERRIDE, (next hop, out NetIf) = (d_via[i].next_hop, d_via[i].wan_netif) and the
+ * route id is not consulted; a wan_netif >= n_netifs gives NONE. Everything after that point is
+ * halo_arp_encap_device's: LOOPBACK against netif[out].ip with the in NetIf's nat_enable, target =
+ * next hop when nonzero else dst, OWN_IP / MISS / HIT. d_via: 8-byte aligned; NULL: the results
+ * equal halo_arp_encap_device's. */
+HALO_API int halo_arp_encap_via_device(const halo_arp_table_t* t, uint8_t* d_bytes, const uint32_t* d_offsets_dw,
+                                       const uint16_t* d_lens, uint32_t n, const uint32_t* d_route_ids,
+                                       uint32_t in_netif, const uint8_t* d_select, const halo_pmflow_via_t* d_via,
+                                       halo_arp_result_t* d_results, uint32_t* d_counts, uint32_t* d_miss_count,
+                                       halo_stream_t stream);
 
 /* ---- egress: per-port transmit streams in ring-record form -----------------------------------
  * The forward path's last step: TxEthernet -> BuildEthFrm (zero-pad to 60 bytes) -> EthTxFunc ->
@@ -1319,7 +1498,7 @@ HALO_API int halo_rx_dispatch_loopback(const halo_rx_result_t* results, uint32_t
  * halo_arp_encap_tx_device -> halo_tx_egress_arp_device. A reply that then gets NO_ROUTE, MISS or
  * OWN_IP has still consumed its iphId (BuildIpv4Pkt runs before FindRoute): build every descriptor,
  * drop afterwards.
- * Not covered: Router.Ipv4PktFwdHook; NatPortMappingFlowTable; DHCP; UDP service replies (the
+ * Not covered: Router.Ipv4PktFwdHook; DHCP; UDP service replies (the
  * handlers' job); sending the LoChan copy of a LOOPBACK reply.
  * The device call: three launches on `stream` (tile counts, scan, scatter), every argument checked
  * before a device is looked for. Alignment: d_records 16; d_desc, d_src 8; offsets, ops, ports map,
