@@ -58,6 +58,32 @@ BOUNDARIES = {
                        test="test_tx_fixup_second_trip[hint 1000]"),
     "tx_g1_trip": dict(kernels="tx_fixup_kernel<1>", file="tx_fixup.hip", constants=("tx_waves",), first_past=4_194_305,
                        test="test_tx_fixup_second_trip[hint 64]"),
+    # halo_tx_build_batch_device: HALO_TXB_MAX_BLOCKS (= HALO_TXB_G1_WAVES * 256) blocks of kBlock / 64 waves, a
+    # 64-descriptor tile per wave and trip whatever the lanes per frame (with HALO_TXB_SPLIT waves per
+    # tile the 16-lane build's cap grows by the same factor)
+    "txb_g1_trip": dict(kernels="tx_build_kernel<1,4>", file="tx_build.hip",
+                        constants=("txb_g1_waves", "txb_blocks_per_wave", "txb_kBlock", "txb_kTile"), first_past=262_145,
+                        test="test_tx_build_second_trip[G1]"),
+    "txb_g4_trip": dict(kernels="tx_build_kernel<4,4>", file="tx_build.hip",
+                        constants=("txb_g1_waves", "txb_blocks_per_wave", "txb_kBlock", "txb_kTile"), first_past=262_145,
+                        test="test_tx_build_second_trip[G4]"),
+    "txb_g8_trip": dict(kernels="tx_build_kernel<8,4>", file="tx_build.hip",
+                        constants=("txb_g1_waves", "txb_blocks_per_wave", "txb_kBlock", "txb_kTile"), first_past=262_145,
+                        test="test_tx_build_second_trip[G8]"),
+    "txb_g16_trip": dict(kernels="tx_build_kernel<16,4>", file="tx_build.hip",
+                         constants=("txb_g1_waves", "txb_blocks_per_wave", "txb_kBlock", "txb_kTile", "txb_split"),
+                         first_past=262_145, test="test_tx_build_second_trip[G16]"),
+    # tx_finish_kernel's full path: every block scans the tile counts txb_finish_pass at a time
+    "txb_finish_pass": dict(kernels="tx_finish_kernel: second scan pass", file="tx_build.hip",
+                            constants=("txb_finish_pass", "txb_kTile"), first_past=65_537,
+                            test="tests/test_gpu_tx_build.py::test_build_rejections_then_clean_launch (n = 70,000); "
+                                 "test_tx_build_second_trip (five passes)"),
+    # tx_build_pair_kernel has no grid-stride loop and no cap: the grid is ceil(n / 512) * 64 blocks of
+    # four waves, a pair of frames per wave. No edge today; its case runs at the grid-stride kernels' n
+    # so that a cap put on that grid meets a test.
+    "txb_pair_grid": dict(kernels="tx_build_pair_kernel<3> (no grid-stride loop: grid = ceil(n / 512) * 64 blocks)",
+                          file="tx_build.hip", constants=("txb_pair_run", "txb_pair_run_blocks", "txb_kBlock"),
+                          first_past=None, test="test_tx_build_second_trip[pair]"),
     # halo_xxh3_64_batch_device's short-string kernel: a wave scans kShortScan strings, a workgroup of
     # four waves 4 * kShortScan, and blocks_for caps the grid at 16,384 workgroups: the second trip
     # begins at 2^24 + 1 strings, beyond the 2^23 strings of <= 16 bytes a test may hold
@@ -98,7 +124,22 @@ def read_constants() -> dict:
     resolve = _one(r"n_tiles < (\d+)u \? n_tiles : (\d+)u", sw)
     rebuild = _one(r"s->slots / 256u < (\d+)u \? s->slots / 256u : (\d+)u", sw)
     assert resolve[0] == resolve[1] and rebuild[0] == rebuild[1]
+    txb = _src("tx_build.hip")
+    # the pair kernel's grid: dim3((uint32_t)(((uint64_t)n + 511u) / 512u * 64u))
+    pair = _one(r"tx_build_pair_kernel<HALO_TXB_BIG_U>\),\s*dim3\(\(uint32_t\)\(\(\(uint64_t\)n \+ (\d+)u\) / (\d+)u \* (\d+)u\)\)",
+                txb)
+    assert int(pair[0]) == int(pair[1]) - 1
+    # the build launch's cap, and that the launch code applies it (times the waves per tile)
+    _one(r"cap = HALO_TXB_MAX_BLOCKS \* split;\s*const dim3 grid\(blocks < cap \? blocks : cap\)", txb)
     return {
+        "txb_g1_waves": int(_one(r"#define HALO_TXB_G1_WAVES (\d+)", txb)),
+        "txb_blocks_per_wave": int(_one(r"#define HALO_TXB_MAX_BLOCKS \(HALO_TXB_G1_WAVES \* (\d+)u\)", txb)),
+        "txb_split": int(_one(r"#define HALO_TXB_SPLIT (\d+)", txb)),
+        "txb_kTile": int(_one(r"constexpr uint32_t kTile = (\d+);", txb)),
+        "txb_kBlock": int(_one(r"constexpr uint32_t kBlock = (\d+);", txb)),
+        "txb_finish_pass": int(_one(r"t0 \+= (\d+)\)", txb)),
+        "txb_pair_run": int(pair[1]),
+        "txb_pair_run_blocks": int(pair[2]),
         "arp_blocks": kmax(arp, "arp_blocks"),
         "nat_blocks": kmax(nat, "nat_blocks"),
         "lpm_blocks": kmax(lpm, "lpm_blocks"),
@@ -119,9 +160,22 @@ def derived(c: dict) -> dict:
     """name -> first n past the boundary, from the constants. Fixed by the kernels' shape and not
     read from the sources: 256 lanes per workgroup, 64 per wave, so a scan pass of `pass` tiles
     gives a lane pass / 256 tiles; 4 addresses per lane in lpm_kernel; 64 / G frames per wave in
-    tx_fixup_kernel<G>; 256 slots per workgroup and trip in sw_rebuild_kernel."""
+    tx_fixup_kernel<G>; 256 slots per workgroup and trip in sw_rebuild_kernel. The build launch
+    (tx_build.hip) is the exception: its block size and tile are read from the source."""
     per_lane = c["arp_pass"] // 256
+    # the build launch: cap blocks of kBlock / 64 waves, a wave per tile (G >= 16: split waves per
+    # tile under a cap split times as large), kTile descriptors per tile
+    txb_waves = c["txb_g1_waves"] * c["txb_blocks_per_wave"] * (c["txb_kBlock"] // 64)
+    txb_trip = txb_waves * c["txb_kTile"] + 1
+    # the pair kernel's grid holds a wave for every pair of frames of every run: nothing to cross
+    assert c["txb_pair_run_blocks"] * (c["txb_kBlock"] // 64) * 2 == c["txb_pair_run"]
     return {
+        "txb_g1_trip": txb_trip,
+        "txb_g4_trip": txb_trip,
+        "txb_g8_trip": txb_trip,
+        "txb_g16_trip": (txb_waves * c["txb_split"]) // c["txb_split"] * c["txb_kTile"] + 1,  # cap x split waves, split per tile
+        "txb_finish_pass": c["txb_finish_pass"] * c["txb_kTile"] + 1,
+        "txb_pair_grid": None,
         "arp_scan_lane": c["kGatherTile"] * per_lane + 1,
         "arp_scan_wave": c["kGatherTile"] * per_lane * 64 + 1,
         "arp_scan_pass": c["kGatherTile"] * c["arp_pass"] + 1,

@@ -505,3 +505,62 @@ def test_tx_fixup_second_trip(dev, oracle_lib, hint, boundary):
         bad = np.nonzero(got != want)[0] if not np.array_equal(got, want) else np.zeros(0, np.int64)
         assert bad.size == 0, f"flag={flag}: {bad.size} bytes differ (first {bad[:8]})"
         assert np.array_equal(res.cpu().numpy(), wres)
+
+
+# ---- tx_build --------------------------------------------------------------------------------------
+TXB_ROWS = {"G1": "txb_g1_trip", "G4": "txb_g4_trip", "G8": "txb_g8_trip", "G16": "txb_g16_trip", "pair": "txb_pair_grid"}
+
+
+def _txb_trip_n():
+    n = S.past("txb_g1_trip", 203)
+    assert all(S.BOUNDARIES[row]["first_past"] in (n - 202, None) for row in TXB_ROWS.values())
+    return n
+
+
+@pytest.fixture(scope="module")
+def txb_trip_want(oracle_lib):
+    """The C oracle's answer for the second-trip batch at full size (once for the five variants), and
+    the slots it implies in a prefilled buffer. Full size: 0.1 s for 262,347 descriptors."""
+    from tests import build_cases as B
+
+    desc, payload = B.second_trip_batch(_txb_trip_n())
+    want = oracle_lib.tx_build_batch(desc, payload, B.MAC, 1, B.TRIP_STRIDE, 0xFFF0)
+    return want, B.expected_slots(*want[:3])
+
+
+@pytest.mark.parametrize("variant", sorted(TXB_ROWS, key=lambda v: (len(v), v)))
+def test_tx_build_second_trip(dev, txb_trip_want, variant):
+    """Each build kernel past the build launch's grid cap (the pair kernel, which has none, at the
+    same n): 262,347 descriptors, so the second trip is three full tiles and one of 11 descriptors.
+    The hint selects the kernel, not the payloads: 0..100 bytes, protocols and modes mixed, 156-byte
+    slots (a multiple of 4, not of 16) prefilled with 0xEE, every 97th descriptor an unknown
+    protocol, one SLOT refusal in the last tile, checksums on, iphId from 0xFFF0. The whole buffer,
+    lengths, results and the final iphId against the oracle: the second trip's tile index and its
+    rejections' ranks, the waves' LDS regions written again behind the closing barrier (G4, G8, G16),
+    the lane kernel's prefetched second-trip descriptors, and the finish kernel renumbering the second
+    trip's frames over five scan passes."""
+    import torch
+
+    from halo_amd._lib import TX_B_OK, TX_B_PROTO, TX_B_SLOT, NetIf
+    from halo_amd.protocol import TxBuilder
+    from tests import build_cases as B
+
+    hint = B.HINTS[variant]
+    assert B.variant_of(hint) == variant
+    n = _txb_trip_n()
+    desc, payload = B.second_trip_batch(n)
+    want, slots = txb_trip_want
+    wr = want[2]
+    first_trip = S.BOUNDARIES["txb_g1_trip"]["first_past"] - 1
+    assert set(wr[first_trip:].tolist()) == {TX_B_OK, TX_B_PROTO, TX_B_SLOT} and TX_B_SLOT in wr[(n - 1) // 64 * 64:]
+    assert int((wr[:first_trip] != TX_B_OK).sum()) > 2000  # the second trip's frames are renumbered
+    assert -(-n // 64) > 4 * S.read_constants()["txb_finish_pass"]  # in the finish kernel's fifth pass
+    assert int(want[1].max()) == 155 and int(B.frame_len(desc)[wr == TX_B_SLOT].min()) == 157
+    b = TxBuilder(n, device=dev, ip_id=0xFFF0)
+    frames = torch.full((n, B.TRIP_STRIDE), B.FILL, dtype=torch.uint8, device=dev)
+    frames, lens, res = b.build(torch.from_numpy(np.array(desc).view(np.uint8)).to(dev), torch.from_numpy(np.array(payload)).to(dev),
+                                netif=NetIf.make(mac="02:00:00:00:00:01", ip="192.168.100.1"), out_stride=B.TRIP_STRIDE,
+                                frames=frames, check_sum_enable=True, max_payload_hint=hint)
+    torch.cuda.synchronize()
+    got = (frames.cpu().numpy(), lens.cpu().numpy().view(np.uint16), res.cpu().numpy(), b.iph_id)
+    B.assert_slots(got, slots, want, f"{variant} (hint {hint}) n={n}", desc)
