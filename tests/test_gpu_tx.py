@@ -1,7 +1,8 @@
 """GPU parity for §8f row f2 (forward / transmit rewrite): halo_tx_fixup_batch_device against
 the committed fixtures and the C oracle, bit-exact over the WHOLE byte buffer (frames, gap
-bytes and tail), for every lanes-per-frame width, plus full-size synthetic batches and the
-rx round trip (rewritten frames verify on the GPU receive path)."""
+bytes and tail), for every lanes-per-frame width, plus full-size synthetic batches, the
+rx round trip (rewritten frames verify on the GPU receive path) and the case table of
+tests/tx_cases.py: option-bearing frames through both summing passes at every width."""
 from __future__ import annotations
 
 import numpy as np
@@ -157,3 +158,62 @@ def test_tx_config2_full_size_round_trip(dev, oracle_lib):
     assert np.all(dead["dst_ip"] == 0x0A000002) and np.all(dead["src_ip"] != 0xC6336401)
     want, _ = oracle_lib.tx_batch(before, lay["offsets_dw"], lay["lens"], ops, flags=1, threads=16)
     assert np.array_equal(fr["bytes"].cpu().numpy(), want)
+
+
+# ---- the sweep: option-bearing frames through both summing passes at every width ------------------
+@pytest.fixture(scope="module")
+def sweep_want(oracle_lib):
+    """(order, flag) -> (cases, layout and ops, the C oracle's buffer and result bytes) of the case
+    table of tests/tx_cases.py: one layout per order and one oracle run per (order, flag), shared."""
+    from tests import tx_cases as T
+
+    lays, wants = {}, {}
+
+    def get(order, flag):
+        c = T.ordered(order)
+        if order not in lays:
+            # (the ops as a writable copy: torch.from_numpy warns about read-only arrays)
+            lays[order] = (*T.layout(c, np.random.default_rng(0x1A70 + T.ORDERS.index(order))), np.array(c.ops))
+        if (order, flag) not in wants:
+            wants[order, flag] = oracle_lib.tx_batch(*lays[order], flags=flag, threads=16)
+        return c, lays[order], wants[order, flag]
+
+    return get
+
+
+@pytest.mark.parametrize("flag", [0, 1])
+@pytest.mark.parametrize("g", [1, 4, 8, 16])
+@pytest.mark.parametrize("order", ["mixed", "uniform"])
+def test_tx_sweep_every_width(dev, sweep_want, order, g, flag):
+    """The whole case table at every lanes-per-frame width, whole buffer and result bytes bit-exact
+    against the C oracle: frames with real IPv4 options (IHL 5..15) from 34 to 1514 bytes whose
+    Go L4 value is seen by the fill's IPv4 sum, so that the kernel's second pass runs with its range
+    ending on both sides of every iteration edge, inside the frame and at odd bytes (no fixture
+    enters that loop, and of the synthetic batches only the few frames whose IHL nibble a bit flip
+    raised: for one iteration, bar two 570-byte frames, and never to an odd end); one lane per frame walks 1500-byte frames through many
+    iterations of both loops and sixteen lanes share 34-byte frames. tests/test_tx_cases.py proves
+    on the CPU what the table reaches. "mixed": every wave mixes plans; "uniform": whole waves of
+    one path class (the wave-uniform arms of the header sums)."""
+    from tests import tx_cases as T
+
+    hint = T.HINTS[g]
+    assert T.width_of(hint) == g
+    c, (data, offs, lens, ops), (want, wres) = sweep_want(order, flag)
+    got, res = _run(dev, data, offs, lens, ops, flag, hint)
+    T.first_difference(c, flag, got, want, offs, res, wres, what=f"GPU tx sweep {order} G{g} flag={flag}")
+
+
+@pytest.mark.parametrize("g", [1, 4, 8, 16])
+def test_tx_sweep_without_result(dev, sweep_want, g):
+    """A null result pointer at every width: the buffer equals the run with a result pointer (and
+    the oracle's)."""
+    from tests import tx_cases as T
+
+    hint = T.HINTS[g]
+    assert T.width_of(hint) == g
+    c, (data, offs, lens, ops), (want, wres) = sweep_want("mixed", 1)
+    with_res, res = _run(dev, data, offs, lens, ops, 1, hint)
+    without, none = _run(dev, data, offs, lens, ops, 1, hint, with_result=False)
+    assert none is None
+    T.first_difference(c, 1, without, with_res, offs, what=f"GPU tx sweep G{g}: no result pointer vs one")
+    T.first_difference(c, 1, without, want, offs, res, wres, what=f"GPU tx sweep G{g}: no result pointer vs oracle")
