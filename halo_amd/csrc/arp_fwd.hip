@@ -20,13 +20,13 @@
 // scan -> scatter, as the switch's probe / scan / admit kernels are.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <new>
 #include <shared_mutex>
 #include <vector>
 
 #include "arp_table.h"
-#include "halo_common.h"
+#include "device_table.h"
+#include "tile_scan.h"
 
 namespace halo {
 namespace {
@@ -46,23 +46,19 @@ struct ArpView {
     uint32_t n_routes;
 };
 
-struct ArpDevice {
-    struct Gen {
-        Slot* d_slots = nullptr;
-        size_t cap = 0;
-        RouteWord* d_routes = nullptr;
-        size_t routes_cap = 0;
-        uint32_t slots = 0, n_routes = 0;
-        bool have_routes = false;
-    } gen[2];
+struct ArpGen {
+    Slot* d_slots = nullptr;
+    size_t cap = 0;
+    RouteWord* d_routes = nullptr;
+    size_t routes_cap = 0;
+    uint32_t slots = 0, n_routes = 0;
+    bool have_routes = false;
+};
+
+struct ArpDevice : Generations<ArpGen> {
     NetIfWord* d_netifs = nullptr;  // HALO_ARP_MAX_NETIFS entries, written once
     std::vector<RouteWord> routes;  // of the last sync: an expiry republishes them
     bool have_routes = false;
-    int device = -1;
-    std::atomic<int> active{-1};  // published generation, -1 before the first sync
-    // Lookups hold it shared from taking their view until their kernel is enqueued; a sync or an
-    // expiry holds it exclusively while it drains the device and rewrites the unpublished generation.
-    std::shared_mutex view_mu;
 };
 
 // The slot holding (netif, ip): its MAC words, or false when the probe chain ends first.
@@ -242,53 +238,14 @@ __device__ __forceinline__ bool is_arp(const halo_rx_result_t* __restrict__ recs
 
 __global__ void __launch_bounds__(kGatherTile) arp_count_kernel(const halo_rx_result_t* __restrict__ recs, uint32_t n,
                                                                 uint32_t* tiles) {
-    __shared__ uint32_t s_sel;
-    if (threadIdx.x == 0) s_sel = 0;
-    __syncthreads();
     const uint32_t i = blockIdx.x * kGatherTile + threadIdx.x;
-    const uint32_t c = (uint32_t)__popcll(__ballot(i < n && is_arp(recs, i)));
-    if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&s_sel, c);
-    __syncthreads();
-    if (threadIdx.x == 0) tiles[blockIdx.x] = s_sel;
+    tile_count(tiles, [&] { return i < n && is_arp(recs, i); });
 }
 
 // One workgroup: tiles[t] becomes the number of messages in the tiles before t; *count = all.
 __global__ void __launch_bounds__(256) arp_scan_kernel(uint32_t* tiles, uint32_t n_tiles, uint32_t* count) {
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_base;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_base = 0;
-    __syncthreads();
-    for (uint32_t t0 = 0; t0 < n_tiles; t0 += 1024) {  // four consecutive tiles per lane and pass
-        const uint32_t t = t0 + 4 * threadIdx.x;
-        uint32_t x[4], sum = 0;
-        for (uint32_t k = 0; k < 4; ++k) {
-            x[k] = t + k < n_tiles ? tiles[t + k] : 0u;
-            sum += x[k];
-        }
-        uint32_t inc = sum;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += y;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t before = s_base;
-        for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
-        uint32_t run = before + inc - sum;
-        for (uint32_t k = 0; k < 4; ++k) {
-            if (t + k < n_tiles) tiles[t + k] = run;
-            run += x[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == 255) s_base = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = s_base;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+    const uint32_t total = scan_tiles(tiles, n_tiles);
+    if (threadIdx.x == 0) *count = total;
 }
 
 __global__ void __launch_bounds__(kGatherTile) arp_scatter_kernel(const uint8_t* __restrict__ bytes,
@@ -296,16 +253,11 @@ __global__ void __launch_bounds__(kGatherTile) arp_scatter_kernel(const uint8_t*
                                                                   const halo_rx_result_t* __restrict__ recs, uint32_t n,
                                                                   uint32_t netif, const uint32_t* __restrict__ tiles,
                                                                   halo_arp_msg_t* __restrict__ msgs, uint32_t cap) {
-    __shared__ uint32_t s_wave[kGatherTile / 64];
     const uint32_t i = blockIdx.x * kGatherTile + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const bool sel = i < n && is_arp(recs, i);
-    const uint64_t b = __ballot(sel);
-    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
+    const uint64_t votes = tile_votes<kGatherTile>(sel);
     if (!sel) return;
-    uint32_t rank = tiles[blockIdx.x] + lanes_below(b);
-    for (uint32_t w = 0; w < wave; ++w) rank += s_wave[w];
+    const uint32_t rank = tile_rank<kGatherTile>(votes, tiles[blockIdx.x]);
     if (rank >= cap) return;
     // a selected frame passed ParseEthFrm: it has at least 42 bytes. Bytes 6-11 and 14-41 only.
     const uint8_t* f = bytes + 4ull * offsets_dw[i];
@@ -328,32 +280,6 @@ uint32_t arp_blocks(uint64_t threads) {
     return (uint32_t)(b > kMax ? kMax : (b ? b : 1));
 }
 
-template <typename T>
-int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return HALO_OK;
-    size_t c = cap ? cap : 256;
-    while (c < need) c *= 2;
-    T* q = nullptr;
-    if (hipMalloc(&q, c * sizeof(T)) != hipSuccess) return HALO_E_NOMEM;
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = c;
-    return HALO_OK;
-}
-
-struct DeviceScope {  // run on `dev`, restore the caller's current device
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceScope() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 ArpDevice* dev_of(const halo_arp_table* t) { return static_cast<ArpDevice*>(t->dev.load(std::memory_order_acquire)); }
 
 // Compile the host table into the unpublished generation and publish it. The caller holds
@@ -361,14 +287,11 @@ ArpDevice* dev_of(const halo_arp_table* t) { return static_cast<ArpDevice*>(t->d
 int publish_locked(halo_arp_table* t, ArpDevice* d) {
     arp::Image img;
     arp::compile(*t, &img);
-    const int cur = d->active.load(std::memory_order_acquire);
-    // the generation written now was last published before `cur`: lookups launched while it was
-    // active may still be running on any stream of the device, so drain the device first
-    if (cur >= 0 && drain_device(d->device) != HALO_OK) return HALO_E_HIP;
-    auto& g = d->gen[cur < 0 ? 0 : 1 - cur];
+    ArpGen* g = d->begin_write();
+    if (!g) return HALO_E_HIP;
     int rc;
-    if ((rc = grow(g.d_slots, g.cap, img.slots.size()))) return rc;
-    if (d->have_routes && (rc = grow(g.d_routes, g.routes_cap, d->routes.size() ? d->routes.size() : 1))) return rc;
+    if ((rc = grow(g->d_slots, g->cap, img.slots.size()))) return rc;
+    if (d->have_routes && (rc = grow(g->d_routes, g->routes_cap, d->routes.size() ? d->routes.size() : 1))) return rc;
     if (!d->d_netifs) {
         NetIfWord w[HALO_ARP_MAX_NETIFS] = {};
         for (uint32_t q = 0; q < t->cfg.n_netifs; ++q) {
@@ -380,18 +303,15 @@ int publish_locked(halo_arp_table* t, ArpDevice* d) {
         if (hipMalloc(&d->d_netifs, sizeof w) != hipSuccess) return HALO_E_NOMEM;
         if (hipMemcpy(d->d_netifs, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess) return HALO_E_HIP;
     }
-    if (hipMemcpy(g.d_slots, img.slots.data(), img.slots.size() * sizeof(Slot), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(g->d_slots, img.slots.data(), img.slots.size() * sizeof(Slot), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
     if (d->have_routes && !d->routes.empty() &&
-        hipMemcpy(g.d_routes, d->routes.data(), d->routes.size() * sizeof(RouteWord), hipMemcpyHostToDevice) != hipSuccess)
+        hipMemcpy(g->d_routes, d->routes.data(), d->routes.size() * sizeof(RouteWord), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
-    g.slots = (uint32_t)img.slots.size();
-    g.n_routes = (uint32_t)d->routes.size();
-    g.have_routes = d->have_routes;
-    // hipMemcpy from pageable memory returns once the host buffer is consumed, not when the copy
-    // has landed: wait for it before publishing
-    if (drain_device(d->device) != HALO_OK) return HALO_E_HIP;
-    d->active.store(cur < 0 ? 0 : 1 - cur, std::memory_order_release);
+    g->slots = (uint32_t)img.slots.size();
+    g->n_routes = (uint32_t)d->routes.size();
+    g->have_routes = d->have_routes;
+    if ((rc = d->publish())) return rc;
     arp::mark_synced(*t, img.version);
     return HALO_OK;
 }
@@ -400,26 +320,13 @@ int ops_sync(halo_arp_table* t, const halo_route_table_t* routes, int device) {
     std::lock_guard<std::mutex> sg(t->sync_mu);
     ArpDevice* d = dev_of(t);
     if (d && d->device != device) return HALO_E_INVAL;  // one device per table
-    {
-        int cnt = 0;
-        if (hipGetDeviceCount(&cnt) != hipSuccess || device >= cnt) {
-            (void)hipGetLastError();
-            return HALO_E_NODEV;
-        }
-    }
-    DeviceScope ds(device);
     int rc;
+    if ((rc = device_present(device))) return rc;
+    DeviceScope ds(device);
     if ((rc = check_device())) return rc;
     std::vector<RouteWord> rw;
-    if (routes) {  // ids are dense and never reused: 0, 1, ... until HALO_E_RANGE
-        for (uint32_t id = 0;; ++id) {
-            halo_route_entry_t e;
-            rc = halo_route_get(routes, id, &e);
-            if (rc == HALO_E_RANGE) break;
-            if (rc) return rc;
-            rw.push_back(RouteWord{e.next_hop, e.netif});
-        }
-    }
+    if (routes && (rc = route_words(routes, &rw, [](const halo_route_entry_t& e) { return RouteWord{e.next_hop, e.netif}; })))
+        return rc;
     if (!d) {
         d = new (std::nothrow) ArpDevice;
         if (!d) return HALO_E_NOMEM;
@@ -435,7 +342,7 @@ int ops_sync(halo_arp_table* t, const halo_route_table_t* routes, int device) {
 
 int ops_publish(halo_arp_table* t) {  // halo_arp_expire after it removed entries, t->sync_mu held
     ArpDevice* d = dev_of(t);
-    if (!d || d->active.load(std::memory_order_acquire) < 0) return HALO_OK;  // never synced: nothing to rebuild
+    if (!d || !d->published()) return HALO_OK;  // never synced: nothing to rebuild
     DeviceScope ds(d->device);
     ParkResidents park(d->device);
     std::unique_lock<std::shared_mutex> vl(d->view_mu);
@@ -461,10 +368,9 @@ void ops_destroy(halo_arp_table* t) {
 
 // The view of the published generation; the caller holds view_mu shared until its launch.
 int arp_view(const halo_arp_table* t, ArpDevice* d, ArpView* out) {
-    const int a = d->active.load(std::memory_order_acquire);
-    if (a < 0) return HALO_E_INVAL;  // never synced
-    const auto& g = d->gen[a];
-    *out = ArpView{g.d_slots, d->d_netifs, g.have_routes ? g.d_routes : nullptr, g.slots - 1, t->cfg.n_netifs, g.n_routes};
+    const ArpGen* g = d->published();
+    if (!g) return HALO_E_INVAL;  // never synced
+    *out = ArpView{g->d_slots, d->d_netifs, g->have_routes ? g->d_routes : nullptr, g->slots - 1, t->cfg.n_netifs, g->n_routes};
     return HALO_OK;
 }
 

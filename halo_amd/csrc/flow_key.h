@@ -77,5 +77,32 @@ HALO_FLOWKEY_FN uint64_t nat_hash(uint32_t proto, uint32_t src, uint32_t dst, ui
     return key_hash(nat_key(proto, src, dst, sport, dport, kind, nat_type));
 }
 
+// The tag word of a used slot of a device flow table (nat_table.h, pmflow_table.h) is
+// kSlotUsed | proto; 0 = empty.
+constexpr uint32_t kSlotUsed = 0x80000000u;
+
+#if defined(__HIPCC__)
+// One probe sequence over a table of mask + 1 32-byte slots {rip, lip, rport | lport << 16, tag;
+// four value words}, placed by linear probing from key_hash & mask: the value words of the slot
+// whose key equals k, or false when the chain ends (an empty slot) first. One aligned 32-byte slot
+// per step, as two 16-byte loads of one sector.
+__device__ __forceinline__ bool probe(const uint4* __restrict__ tab, uint32_t mask, const Key& k, uint4* hit) {
+    const uint32_t ports = k.rport | k.lport << 16, tag = kSlotUsed | k.proto;
+    uint32_t s = (uint32_t)key_hash(k) & mask;
+    for (uint32_t step = 0; step <= mask; ++step) {  // bounded: a full table cannot spin
+        const uint4* p = tab + 2ull * s;
+        const uint4 key = p[0];
+        const uint4 val = p[1];
+        if (key.w == 0) return false;
+        if (key.x == k.rip && key.y == k.lip && key.z == ports && key.w == tag) {
+            *hit = val;
+            return true;
+        }
+        s = (s + 1) & mask;
+    }
+    return false;
+}
+#endif
+
 }  // namespace flowkey
 }  // namespace halo

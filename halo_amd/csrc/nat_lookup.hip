@@ -18,13 +18,12 @@
 // address, a broadcast; misses are counted per wavefront with a ballot and one atomic add.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <new>
 #include <shared_mutex>
 #include <vector>
 
+#include "device_table.h"
 #include "flow_key.h"
-#include "halo_common.h"
 #include "nat_table.h"
 
 namespace halo {
@@ -34,7 +33,7 @@ using nat::MapWord;
 using nat::Slot;
 
 struct NatView {
-    const Slot* index[2];  // [HALO_FLOW_NAT_LAN], [HALO_FLOW_NAT_WAN]
+    const uint4* index[2];  // [HALO_FLOW_NAT_LAN], [HALO_FLOW_NAT_WAN]: 32-byte Slots as flowkey::probe reads them
     const MapWord* maps;
     uint32_t* stamps;
     uint32_t mask;    // slots - 1
@@ -43,41 +42,16 @@ struct NatView {
     uint32_t wan_ip;
 };
 
-struct NatDevice {
-    struct Gen {
-        Slot* d_index[2] = {nullptr, nullptr};
-        size_t cap[2] = {0, 0};
-        MapWord* d_maps = nullptr;  // HALO_NAT_MAX_PORT_MAPPINGS entries
-        uint32_t slots = 0, n_maps = 0;
-    } gen[2];
-    uint32_t* d_stamps = nullptr;  // by flow id; shared by both generations
-    size_t stamps_cap = 0;
-    uint32_t n_stamps = 0;  // ids the device copy knows (next_id at the last sync)
-    int device = -1;
-    std::atomic<int> active{-1};  // published generation, -1 before the first sync
-    // Lookups hold it shared from taking their view until their kernel is enqueued; a sync or a
-    // fold holds it exclusively while it drains the device, reads the stamps back and rewrites
-    // the unpublished generation.
-    std::shared_mutex view_mu;
+struct NatGen {
+    Slot* d_index[2] = {nullptr, nullptr};
+    size_t cap[2] = {0, 0};
+    MapWord* d_maps = nullptr;  // HALO_NAT_MAX_PORT_MAPPINGS entries
+    uint32_t slots = 0, n_maps = 0;
 };
 
-// One probe sequence: the slot whose key equals (k0..k3), or tag 0 when the chain ends.
-__device__ __forceinline__ bool probe(const Slot* __restrict__ idx, uint32_t mask, const flowkey::Key& k, uint4* hit) {
-    const uint32_t ports = k.rport | k.lport << 16, tag = nat::kSlotUsed | k.proto;
-    uint32_t s = (uint32_t)flowkey::key_hash(k) & mask;
-    for (uint32_t step = 0; step <= mask; ++step) {  // bounded: a full index cannot spin
-        const uint4* p = reinterpret_cast<const uint4*>(idx + s);
-        const uint4 key = p[0];
-        const uint4 val = p[1];
-        if (key.w == 0) return false;
-        if (key.x == k.rip && key.y == k.lip && key.z == ports && key.w == tag) {
-            *hit = val;  // x_ip, x_port, id
-            return true;
-        }
-        s = (s + 1) & mask;
-    }
-    return false;
-}
+struct NatDevice : Generations<NatGen> {
+    Stamps stamps;
+};
 
 // KIND: HALO_FLOW_NAT_WAN = inbound half (DNAT), HALO_FLOW_NAT_LAN = outbound half (SNAT)
 template <uint32_t KIND, bool COMPACT>
@@ -131,7 +105,7 @@ __global__ void __launch_bounds__(256) nat_lookup_kernel(const NatView v, const 
                 if (verd == HALO_NAT_V_MISS) {
                     const flowkey::Key k = flowkey::nat_key(proto, src, dst, sport, dport, KIND, v.nat_type);
                     uint4 hit;
-                    if (probe(v.index[KIND], v.mask, k, &hit)) {
+                    if (flowkey::probe(v.index[KIND], v.mask, k, &hit)) {  // x_ip, x_port, id
                         verd = HALO_NAT_V_FLOW;
                         x_ip = hit.x, x_port = hit.y, rf = hit.z;
                         v.stamps[rf] = now;  // LastAliveTime = TimeNow (:125, :219)
@@ -172,7 +146,7 @@ __global__ void __launch_bounds__(256) nat_quote_kernel(const NatView v, const h
             const flowkey::Key k =
                 flowkey::nat_key(r.y & 0xFFu, r.z, r.w, ports & 0xFFFFu, ports >> 16, HALO_FLOW_NAT_WAN, v.nat_type);
             uint4 hit;
-            if (probe(v.index[HALO_FLOW_NAT_WAN], v.mask, k, &hit)) o = make_uint2(hit.x, (hit.y & 0xFFFFu) | 1u << 16);
+            if (flowkey::probe(v.index[HALO_FLOW_NAT_WAN], v.mask, k, &hit)) o = make_uint2(hit.x, (hit.y & 0xFFFFu) | 1u << 16);
         }
         reinterpret_cast<uint2*>(out)[i] = o;
     }
@@ -184,44 +158,15 @@ uint32_t nat_blocks(uint64_t threads) {
     return (uint32_t)(b > kMax ? kMax : (b ? b : 1));
 }
 
-template <typename T>
-int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return HALO_OK;
-    size_t c = cap ? cap : 256;
-    while (c < need) c *= 2;
-    T* q = nullptr;
-    if (hipMalloc(&q, c * sizeof(T)) != hipSuccess) return HALO_E_NOMEM;
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = c;
-    return HALO_OK;
-}
-
-struct DeviceScope {  // run on `dev`, restore the caller's current device
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceScope() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 NatDevice* dev_of(const halo_nat_table* t) { return static_cast<NatDevice*>(t->dev.load(std::memory_order_acquire)); }
 
 // Drain the device and merge the stamps it wrote into the host table. view_mu held exclusively.
 int fold_locked(halo_nat_table* t, NatDevice* d) {
-    if (d->active.load(std::memory_order_acquire) < 0) return HALO_OK;
-    if (drain_device(d->device) != HALO_OK) return HALO_E_HIP;
-    if (d->n_stamps == 0) return HALO_OK;
-    std::vector<uint32_t> back(d->n_stamps);
-    if (hipMemcpy(back.data(), d->d_stamps, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return HALO_E_HIP;
-    nat::merge_stamps(*t, back.data(), d->n_stamps);
-    return HALO_OK;
+    if (!d->published()) return HALO_OK;
+    std::vector<uint32_t> back;
+    const int rc = d->stamps.read_back(d->device, &back);
+    if (!rc && !back.empty()) nat::merge_stamps(*t, back.data(), (uint32_t)back.size());
+    return rc;
 }
 
 // Compile the host table into the unpublished generation and publish it. The caller holds
@@ -230,45 +175,26 @@ int publish_locked(halo_nat_table* t, NatDevice* d) {
     nat::Image img;
     int rc = nat::compile(*t, &img, true);
     if (rc) return rc;
-    const int cur = d->active.load(std::memory_order_acquire);
-    // the generation written now was last published before `cur`: lookups launched while it was
-    // active may still be running on any stream of the device, so drain the device first
-    if (cur >= 0 && drain_device(d->device) != HALO_OK) return HALO_E_HIP;
-    auto& g = d->gen[cur < 0 ? 0 : 1 - cur];
+    NatGen* g = d->begin_write();
+    if (!g) return HALO_E_HIP;
     for (int k = 0; k < 2; ++k)
-        if ((rc = grow(g.d_index[k], g.cap[k], img.slots))) return rc;
-    if (!g.d_maps && hipMalloc(&g.d_maps, HALO_NAT_MAX_PORT_MAPPINGS * sizeof(MapWord)) != hipSuccess) return HALO_E_NOMEM;
-    // the stamp array is shared: growing it replaces it for both generations, which is safe only
-    // because the device is drained and no lookup can take a view (view_mu) until we return
-    if (img.stamps.size() > d->stamps_cap) {
-        if (cur >= 0 && drain_device(d->device) != HALO_OK) return HALO_E_HIP;
-        if ((rc = grow(d->d_stamps, d->stamps_cap, img.stamps.size()))) return rc;
-    } else if (!d->d_stamps && (rc = grow(d->d_stamps, d->stamps_cap, 1))) {
-        return rc;
-    }
+        if ((rc = grow(g->d_index[k], g->cap[k], img.slots))) return rc;
+    if (!g->d_maps && hipMalloc(&g->d_maps, HALO_NAT_MAX_PORT_MAPPINGS * sizeof(MapWord)) != hipSuccess) return HALO_E_NOMEM;
     for (int k = 0; k < 2; ++k)
-        if (hipMemcpy(g.d_index[k], img.index[k].data(), (size_t)img.slots * sizeof(Slot), hipMemcpyHostToDevice) != hipSuccess)
+        if (hipMemcpy(g->d_index[k], img.index[k].data(), (size_t)img.slots * sizeof(Slot), hipMemcpyHostToDevice) != hipSuccess)
             return HALO_E_HIP;
     if (!img.maps.empty() &&
-        hipMemcpy(g.d_maps, img.maps.data(), img.maps.size() * sizeof(MapWord), hipMemcpyHostToDevice) != hipSuccess)
+        hipMemcpy(g->d_maps, img.maps.data(), img.maps.size() * sizeof(MapWord), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
-    // every live flow's merged stamp (the fold ran under the same lock, so nothing newer exists on
-    // the device); a new flow's slot thereby starts from its host stamp
-    if (!img.stamps.empty() &&
-        hipMemcpy(d->d_stamps, img.stamps.data(), img.stamps.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-        return HALO_E_HIP;
-    g.slots = img.slots;
-    g.n_maps = (uint32_t)img.maps.size();
-    d->n_stamps = (uint32_t)img.stamps.size();
-    // hipMemcpy from pageable memory returns once the host buffer is consumed, not when the copy
-    // has landed: wait for it before publishing
-    if (drain_device(d->device) != HALO_OK) return HALO_E_HIP;
-    d->active.store(cur < 0 ? 0 : 1 - cur, std::memory_order_release);
-    return HALO_OK;
+    if ((rc = d->stamps.upload(img.stamps))) return rc;
+    g->slots = img.slots;
+    g->n_maps = (uint32_t)img.maps.size();
+    return d->publish();
 }
 
 int ops_fold(halo_nat_table* t) {  // halo_nat_expire, t->sync_mu held
     NatDevice* d = dev_of(t);
+    if (!d) return HALO_OK;
     DeviceScope ds(d->device);
     ParkResidents park(d->device);
     std::unique_lock<std::shared_mutex> vl(d->view_mu);
@@ -277,7 +203,7 @@ int ops_fold(halo_nat_table* t) {  // halo_nat_expire, t->sync_mu held
 
 int ops_publish(halo_nat_table* t) {  // halo_nat_expire after it removed flows, t->sync_mu held
     NatDevice* d = dev_of(t);
-    if (d->active.load(std::memory_order_acquire) < 0) return HALO_OK;  // never synced: nothing to rebuild
+    if (!d || !d->published()) return HALO_OK;  // never synced: nothing to rebuild
     DeviceScope ds(d->device);
     ParkResidents park(d->device);
     std::unique_lock<std::shared_mutex> vl(d->view_mu);
@@ -298,7 +224,7 @@ void ops_destroy(halo_nat_table* t) {
                 if (p) (void)hipFree(p);
             if (g.d_maps) (void)hipFree(g.d_maps);
         }
-        if (d->d_stamps) (void)hipFree(d->d_stamps);
+        if (d->stamps.d_stamps) (void)hipFree(d->stamps.d_stamps);
     }
     delete d;
     t->dev.store(nullptr, std::memory_order_release);
@@ -308,11 +234,10 @@ const nat::DeviceOps kDeviceOps = {ops_fold, ops_publish, ops_destroy};
 
 // The view of the published generation; the caller holds view_mu shared until its launch.
 int nat_view(const halo_nat_table* t, NatDevice* d, NatView* out) {
-    const int a = d->active.load(std::memory_order_acquire);
-    if (a < 0) return HALO_E_INVAL;  // never synced
-    const auto& g = d->gen[a];
-    *out = NatView{{g.d_index[0], g.d_index[1]}, g.d_maps, d->d_stamps, g.slots - 1, g.n_maps, t->cfg.nat_type,
-                   t->cfg.wan_ip};
+    const NatGen* g = d->published();
+    if (!g) return HALO_E_INVAL;  // never synced
+    *out = NatView{{reinterpret_cast<const uint4*>(g->d_index[0]), reinterpret_cast<const uint4*>(g->d_index[1])},
+                   g->d_maps, d->stamps.d_stamps, g->slots - 1, g->n_maps, t->cfg.nat_type, t->cfg.wan_ip};
     return HALO_OK;
 }
 
@@ -346,12 +271,9 @@ extern "C" HALO_API int halo_nat_sync_device(halo_nat_table_t* t, int device) {
     std::lock_guard<std::mutex> sg(t->sync_mu);
     halo::NatDevice* d = halo::dev_of(t);
     if (d && d->device >= 0 && d->device != device) return HALO_E_INVAL;  // one device per table
-    {
-        int cnt = 0;
-        if (hipGetDeviceCount(&cnt) != hipSuccess || device >= cnt) return HALO_E_NODEV;
-    }
-    halo::DeviceScope ds(device);
     int rc;
+    if ((rc = halo::device_present(device))) return rc;
+    halo::DeviceScope ds(device);
     if ((rc = halo::check_device())) return rc;
     if (!d) {
         d = new (std::nothrow) halo::NatDevice;

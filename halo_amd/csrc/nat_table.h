@@ -65,7 +65,7 @@ struct alignas(32) Slot {
     uint32_t pad;
 };
 static_assert(sizeof(Slot) == 32, "slot");
-constexpr uint32_t kSlotUsed = 0x80000000u;
+using flowkey::kSlotUsed;
 // a port mapping as the kernels stage it in LDS (12 bytes)
 struct MapWord {
     uint32_t ports;  // wan_port | lan_port << 16

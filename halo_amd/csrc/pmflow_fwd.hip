@@ -20,32 +20,29 @@
 // flag byte per frame, so the scatter does not probe again.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <new>
 #include <shared_mutex>
 #include <vector>
 
 #include "arp_table.h"
+#include "device_table.h"
 #include "flow_key.h"
-#include "halo_common.h"
 #include "pmflow_table.h"
+#include "tile_scan.h"
 
 namespace halo {
 namespace {
 
 using pmflow::kRecordTile;
-using pmflow::kScanPass;
-using pmflow::kSlotUsed;
 using pmflow::NetIfWord;
 using pmflow::Slot;
 
 // the listing shares its tile and scan geometry with the ARP gather: one set of boundary sizes
 static_assert(kRecordTile == arp::kGatherTile, "record tile == the ARP gather's tile");
-static_assert(kScanPass == 4 * 256, "scan pass == four tiles per lane of a 256-lane workgroup");
 static_assert(kRecordTile % 64 == 0, "whole wavefronts per tile");
 
 struct PmView {
-    const Slot* slots;
+    const uint4* slots;  // 32-byte Slots as flowkey::probe reads them
     const NetIfWord* netifs;
     const uint32_t* route_netif;  // null: synced without a route table
     uint32_t* stamps;
@@ -54,47 +51,21 @@ struct PmView {
     uint32_t n_routes;
 };
 
-struct PmDevice {
-    struct Gen {
-        Slot* d_slots = nullptr;
-        size_t cap = 0;
-        uint32_t* d_routes = nullptr;
-        size_t routes_cap = 0;
-        uint32_t slots = 0, n_routes = 0;
-        bool have_routes = false;
-    } gen[2];
-    NetIfWord* d_netifs = nullptr;  // HALO_ARP_MAX_NETIFS entries, written once
-    uint32_t* d_stamps = nullptr;   // by flow id; shared by both generations
-    size_t stamps_cap = 0;
-    uint32_t n_stamps = 0;            // ids the device copy knows (next_id at the last publish)
-    std::vector<uint32_t> routes;     // of the last sync: an expiry republishes them
+struct PmGen {
+    Slot* d_slots = nullptr;
+    size_t cap = 0;
+    uint32_t* d_routes = nullptr;
+    size_t routes_cap = 0;
+    uint32_t slots = 0, n_routes = 0;
     bool have_routes = false;
-    int device = -1;
-    std::atomic<int> active{-1};  // published generation, -1 before the first sync
-    // Lookups hold it shared from taking their view until their kernel is enqueued; a sync, a fold
-    // or an expiry holds it exclusively while it drains the device, reads the stamps back and
-    // rewrites the unpublished generation.
-    std::shared_mutex view_mu;
 };
 
-// One probe sequence: the value words {wan_netif, wan_port, id, pad} of the slot whose key equals
-// k, or false when the chain ends first.
-__device__ __forceinline__ bool probe(const Slot* __restrict__ tab, uint32_t mask, const flowkey::Key& k, uint4* hit) {
-    const uint32_t ports = k.rport | k.lport << 16, tag = kSlotUsed | k.proto;
-    uint32_t s = (uint32_t)flowkey::key_hash(k) & mask;
-    for (uint32_t step = 0; step <= mask; ++step) {  // bounded: a full table cannot spin
-        const uint4* p = reinterpret_cast<const uint4*>(tab + s);
-        const uint4 key = p[0];
-        const uint4 val = p[1];
-        if (key.w == 0) return false;
-        if (key.x == k.rip && key.y == k.lip && key.z == ports && key.w == tag) {
-            *hit = val;
-            return true;
-        }
-        s = (s + 1) & mask;
-    }
-    return false;
-}
+struct PmDevice : Generations<PmGen> {
+    NetIfWord* d_netifs = nullptr;  // HALO_ARP_MAX_NETIFS entries, written once
+    Stamps stamps;
+    std::vector<uint32_t> routes;  // of the last sync: an expiry republishes them
+    bool have_routes = false;
+};
 
 __global__ void __launch_bounds__(256) pmflow_lookup_kernel(const PmView v, const halo_rx_result_t* __restrict__ recs,
                                                             uint32_t n, uint32_t now,
@@ -125,7 +96,7 @@ __global__ void __launch_bounds__(256) pmflow_lookup_kernel(const PmView v, cons
                 // NatFlowHash{remote = dst : dport, lan host = src : sport} (:165-171); only TCP / UDP
                 // flows exist (CheckNatPortMapping, :683-707)
                 if ((proto == 6u || proto == 17u) &&
-                    probe(v.slots, v.mask, flowkey::Key{dst, ports >> 16, src, ports & 0xFFFFu, proto}, &f)) {
+                    flowkey::probe(v.slots, v.mask, flowkey::Key{dst, ports >> 16, src, ports & 0xFFFFu, proto}, &f)) {
                     v.stamps[f.z] = now;  // LastAliveTime = TimeNow (:176)
                     const uint4 nif = *reinterpret_cast<const uint4*>(v.netifs + f.x);  // ip, nat_enable, gateway
                     // outNetIfName != WanNetIf (:182): a panicking route is the encap's to report
@@ -162,18 +133,12 @@ __device__ __forceinline__ bool is_candidate(const uint8_t* __restrict__ wan_ver
     return wan_verdict[i] == HALO_NAT_V_MAPPING && (arp[i].x & 0xFFu) == HALO_ARP_V_HIT;
 }
 
-// Tile counts; flags[i] = 1 for a frame to list. A candidate the device copy already holds with
-// the same value is stamped here instead.
-__global__ void __launch_bounds__(kRecordTile) pmflow_count_kernel(const PmView v, uint32_t in_netif,
-                                                                   const halo_rx_result_t* __restrict__ recs,
-                                                                   const uint8_t* __restrict__ wan_verdict,
-                                                                   const halo_tx_op_t* __restrict__ ops,
-                                                                   const uint2* __restrict__ arp, uint32_t n, uint32_t now,
-                                                                   uint32_t* tiles, uint8_t* __restrict__ flags) {
-    __shared__ uint32_t s_sel;
-    if (threadIdx.x == 0) s_sel = 0;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * kRecordTile + threadIdx.x;
+// Whether frame i is one to list, also left in flags[i]. A candidate the device copy already holds
+// with the same value is stamped here instead.
+__device__ __forceinline__ bool to_list(const PmView& v, uint32_t in_netif, const halo_rx_result_t* __restrict__ recs,
+                                        const uint8_t* __restrict__ wan_verdict, const halo_tx_op_t* __restrict__ ops,
+                                        const uint2* __restrict__ arp, uint32_t n, uint32_t now, uint8_t* __restrict__ flags,
+                                        uint32_t i) {
     bool list = false;
     if (i < n) {
         if (is_candidate(wan_verdict, arp, i)) {
@@ -183,7 +148,7 @@ __global__ void __launch_bounds__(kRecordTile) pmflow_count_kernel(const PmView 
             uint4 f;
             list = true;
             // NatFlowHash{remote = src : sport, lan host = the entry's} (:240-247)
-            if (probe(v.slots, v.mask, flowkey::Key{r.z, ports & 0xFFFFu, op.y, op.x >> 16, r.y & 0xFFu}, &f) &&
+            if (flowkey::probe(v.slots, v.mask, flowkey::Key{r.z, ports & 0xFFFFu, op.y, op.x >> 16, r.y & 0xFFu}, &f) &&
                 f.x == in_netif && f.y == (ports >> 16)) {
                 v.stamps[f.z] = now;  // :264; WanNetIf and WanPort are already these
                 list = false;
@@ -191,49 +156,24 @@ __global__ void __launch_bounds__(kRecordTile) pmflow_count_kernel(const PmView 
         }
         flags[i] = list ? 1 : 0;
     }
-    const uint32_t c = (uint32_t)__popcll(__ballot(list));
-    if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&s_sel, c);
-    __syncthreads();
-    if (threadIdx.x == 0) tiles[blockIdx.x] = s_sel;
+    return list;
+}
+
+// Tile counts of the frames to list.
+__global__ void __launch_bounds__(kRecordTile) pmflow_count_kernel(const PmView v, uint32_t in_netif,
+                                                                   const halo_rx_result_t* __restrict__ recs,
+                                                                   const uint8_t* __restrict__ wan_verdict,
+                                                                   const halo_tx_op_t* __restrict__ ops,
+                                                                   const uint2* __restrict__ arp, uint32_t n, uint32_t now,
+                                                                   uint32_t* tiles, uint8_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * kRecordTile + threadIdx.x;
+    tile_count(tiles, [&] { return to_list(v, in_netif, recs, wan_verdict, ops, arp, n, now, flags, i); });
 }
 
 // One workgroup: tiles[t] becomes the number of items in the tiles before t; *count = all.
 __global__ void __launch_bounds__(256) pmflow_scan_kernel(uint32_t* tiles, uint32_t n_tiles, uint32_t* count) {
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_base;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_base = 0;
-    __syncthreads();
-    for (uint32_t t0 = 0; t0 < n_tiles; t0 += kScanPass) {  // four consecutive tiles per lane and pass
-        const uint32_t t = t0 + 4 * threadIdx.x;
-        uint32_t x[4], sum = 0;
-        for (uint32_t k = 0; k < 4; ++k) {
-            x[k] = t + k < n_tiles ? tiles[t + k] : 0u;
-            sum += x[k];
-        }
-        uint32_t inc = sum;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += y;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t before = s_base;
-        for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
-        uint32_t run = before + inc - sum;
-        for (uint32_t k = 0; k < 4; ++k) {
-            if (t + k < n_tiles) tiles[t + k] = run;
-            run += x[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == 255) s_base = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = s_base;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+    const uint32_t total = scan_tiles(tiles, n_tiles);
+    if (threadIdx.x == 0) *count = total;
 }
 
 __global__ void __launch_bounds__(kRecordTile) pmflow_scatter_kernel(const halo_rx_result_t* __restrict__ recs,
@@ -241,16 +181,11 @@ __global__ void __launch_bounds__(kRecordTile) pmflow_scatter_kernel(const halo_
                                                                      const uint32_t* __restrict__ tiles,
                                                                      const uint8_t* __restrict__ flags,
                                                                      halo_pmflow_item_t* __restrict__ items, uint32_t cap) {
-    __shared__ uint32_t s_wave[kRecordTile / 64];
     const uint32_t i = blockIdx.x * kRecordTile + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const bool sel = i < n && flags[i];
-    const uint64_t b = __ballot(sel);
-    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
+    const uint64_t votes = tile_votes<kRecordTile>(sel);
     if (!sel) return;
-    uint32_t rank = tiles[blockIdx.x] + lanes_below(b);
-    for (uint32_t w = 0; w < wave; ++w) rank += s_wave[w];
+    const uint32_t rank = tile_rank<kRecordTile>(votes, tiles[blockIdx.x]);
     if (rank >= cap) return;
     const uint4 r = reinterpret_cast<const uint4*>(recs)[2ull * i];
     const uint32_t ports = reinterpret_cast<const uint32_t*>(recs)[8ull * i + 4];
@@ -278,44 +213,15 @@ uint32_t pm_blocks(uint64_t threads) {
     return (uint32_t)(b > kMax ? kMax : (b ? b : 1));
 }
 
-template <typename T>
-int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return HALO_OK;
-    size_t c = cap ? cap : 256;
-    while (c < need) c *= 2;
-    T* q = nullptr;
-    if (hipMalloc(&q, c * sizeof(T)) != hipSuccess) return HALO_E_NOMEM;
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = c;
-    return HALO_OK;
-}
-
-struct DeviceScope {  // run on `dev`, restore the caller's current device
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceScope() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 PmDevice* dev_of(const halo_pmflow_table* t) { return static_cast<PmDevice*>(t->dev.load(std::memory_order_acquire)); }
 
 // Drain the device and merge the stamps it wrote into the host table. view_mu held exclusively.
 int fold_locked(halo_pmflow_table* t, PmDevice* d) {
-    if (d->active.load(std::memory_order_acquire) < 0) return HALO_OK;
-    if (drain_device(d->device) != HALO_OK) return HALO_E_HIP;
-    if (d->n_stamps == 0) return HALO_OK;
-    std::vector<uint32_t> back(d->n_stamps);
-    if (hipMemcpy(back.data(), d->d_stamps, back.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return HALO_E_HIP;
-    pmflow::merge_stamps(*t, back.data(), d->n_stamps);
-    return HALO_OK;
+    if (!d->published()) return HALO_OK;
+    std::vector<uint32_t> back;
+    const int rc = d->stamps.read_back(d->device, &back);
+    if (!rc && !back.empty()) pmflow::merge_stamps(*t, back.data(), (uint32_t)back.size());
+    return rc;
 }
 
 // Compile the host table into the unpublished generation and publish it. The caller holds
@@ -324,13 +230,10 @@ int publish_locked(halo_pmflow_table* t, PmDevice* d) {
     pmflow::Image img;
     int rc = pmflow::compile(*t, &img, true);
     if (rc) return rc;
-    const int cur = d->active.load(std::memory_order_acquire);
-    // the generation written now was last published before `cur`: lookups launched while it was
-    // active may still be running on any stream of the device, so drain the device first
-    if (cur >= 0 && drain_device(d->device) != HALO_OK) return HALO_E_HIP;
-    auto& g = d->gen[cur < 0 ? 0 : 1 - cur];
-    if ((rc = grow(g.d_slots, g.cap, img.slots.size()))) return rc;
-    if (d->have_routes && (rc = grow(g.d_routes, g.routes_cap, d->routes.size() ? d->routes.size() : 1))) return rc;
+    PmGen* g = d->begin_write();
+    if (!g) return HALO_E_HIP;
+    if ((rc = grow(g->d_slots, g->cap, img.slots.size()))) return rc;
+    if (d->have_routes && (rc = grow(g->d_routes, g->routes_cap, d->routes.size() ? d->routes.size() : 1))) return rc;
     if (!d->d_netifs) {
         NetIfWord w[HALO_ARP_MAX_NETIFS] = {};
         for (uint32_t q = 0; q < t->cfg.n_netifs; ++q)
@@ -338,27 +241,16 @@ int publish_locked(halo_pmflow_table* t, PmDevice* d) {
         if (hipMalloc(&d->d_netifs, sizeof w) != hipSuccess) return HALO_E_NOMEM;
         if (hipMemcpy(d->d_netifs, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess) return HALO_E_HIP;
     }
-    // the stamp array is shared: growing it replaces it for both generations, which is safe only
-    // because the device is drained and no lookup can take a view (view_mu) until we return
-    if ((rc = grow(d->d_stamps, d->stamps_cap, img.stamps.size() ? img.stamps.size() : 1))) return rc;
-    if (hipMemcpy(g.d_slots, img.slots.data(), img.slots.size() * sizeof(Slot), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(g->d_slots, img.slots.data(), img.slots.size() * sizeof(Slot), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
     if (d->have_routes && !d->routes.empty() &&
-        hipMemcpy(g.d_routes, d->routes.data(), d->routes.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+        hipMemcpy(g->d_routes, d->routes.data(), d->routes.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
-    // every live flow's merged stamp (the fold ran under the same lock, so nothing newer exists on
-    // the device); a new flow's slot thereby starts from its host stamp
-    if (!img.stamps.empty() &&
-        hipMemcpy(d->d_stamps, img.stamps.data(), img.stamps.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-        return HALO_E_HIP;
-    g.slots = (uint32_t)img.slots.size();
-    g.n_routes = (uint32_t)d->routes.size();
-    g.have_routes = d->have_routes;
-    d->n_stamps = (uint32_t)img.stamps.size();
-    // hipMemcpy from pageable memory returns once the host buffer is consumed, not when the copy
-    // has landed: wait for it before publishing
-    if (drain_device(d->device) != HALO_OK) return HALO_E_HIP;
-    d->active.store(cur < 0 ? 0 : 1 - cur, std::memory_order_release);
+    if ((rc = d->stamps.upload(img.stamps))) return rc;
+    g->slots = (uint32_t)img.slots.size();
+    g->n_routes = (uint32_t)d->routes.size();
+    g->have_routes = d->have_routes;
+    if ((rc = d->publish())) return rc;
     pmflow::mark_synced(*t, img.version);
     return HALO_OK;
 }
@@ -367,26 +259,12 @@ int ops_sync(halo_pmflow_table* t, const halo_route_table_t* routes, int device)
     std::lock_guard<std::mutex> sg(t->sync_mu);
     PmDevice* d = dev_of(t);
     if (d && d->device != device) return HALO_E_INVAL;  // one device per table
-    {
-        int cnt = 0;
-        if (hipGetDeviceCount(&cnt) != hipSuccess || device >= cnt) {
-            (void)hipGetLastError();
-            return HALO_E_NODEV;
-        }
-    }
-    DeviceScope ds(device);
     int rc;
+    if ((rc = device_present(device))) return rc;
+    DeviceScope ds(device);
     if ((rc = check_device())) return rc;
     std::vector<uint32_t> rw;
-    if (routes) {  // ids are dense and never reused: 0, 1, ... until HALO_E_RANGE
-        for (uint32_t id = 0;; ++id) {
-            halo_route_entry_t e;
-            rc = halo_route_get(routes, id, &e);
-            if (rc == HALO_E_RANGE) break;
-            if (rc) return rc;
-            rw.push_back(e.netif);
-        }
-    }
+    if (routes && (rc = route_words(routes, &rw, [](const halo_route_entry_t& e) { return e.netif; }))) return rc;
     if (!d) {
         d = new (std::nothrow) PmDevice;
         if (!d) return HALO_E_NOMEM;
@@ -412,7 +290,7 @@ int ops_fold(halo_pmflow_table* t) {  // halo_pmflow_expire, t->sync_mu held
 
 int ops_publish(halo_pmflow_table* t) {  // halo_pmflow_expire after it removed flows, t->sync_mu held
     PmDevice* d = dev_of(t);
-    if (!d || d->active.load(std::memory_order_acquire) < 0) return HALO_OK;  // never synced: nothing to rebuild
+    if (!d || !d->published()) return HALO_OK;  // never synced: nothing to rebuild
     DeviceScope ds(d->device);
     ParkResidents park(d->device);
     std::unique_lock<std::shared_mutex> vl(d->view_mu);
@@ -433,7 +311,7 @@ void ops_destroy(halo_pmflow_table* t) {
             if (g.d_routes) (void)hipFree(g.d_routes);
         }
         if (d->d_netifs) (void)hipFree(d->d_netifs);
-        if (d->d_stamps) (void)hipFree(d->d_stamps);
+        if (d->stamps.d_stamps) (void)hipFree(d->stamps.d_stamps);
     }
     delete d;
     t->dev.store(nullptr, std::memory_order_release);
@@ -441,11 +319,10 @@ void ops_destroy(halo_pmflow_table* t) {
 
 // The view of the published generation; the caller holds view_mu shared until its launch.
 int pm_view(const halo_pmflow_table* t, PmDevice* d, PmView* out) {
-    const int a = d->active.load(std::memory_order_acquire);
-    if (a < 0) return HALO_E_INVAL;  // never synced
-    const auto& g = d->gen[a];
-    *out = PmView{g.d_slots, d->d_netifs, g.have_routes ? g.d_routes : nullptr, d->d_stamps, g.slots - 1,
-                  t->cfg.n_netifs, g.n_routes};
+    const PmGen* g = d->published();
+    if (!g) return HALO_E_INVAL;  // never synced
+    *out = PmView{reinterpret_cast<const uint4*>(g->d_slots), d->d_netifs, g->have_routes ? g->d_routes : nullptr,
+                  d->stamps.d_stamps, g->slots - 1, t->cfg.n_netifs, g->n_routes};
     return HALO_OK;
 }
 

@@ -48,7 +48,7 @@ struct alignas(32) Slot {
     uint32_t pad;
 };
 static_assert(sizeof(Slot) == 32, "slot");
-constexpr uint32_t kSlotUsed = 0x80000000u;
+using flowkey::kSlotUsed;
 
 // A NetIf as the kernels read it (16 bytes)
 struct alignas(16) NetIfWord {
@@ -60,10 +60,9 @@ struct alignas(16) NetIfWord {
 
 inline uint32_t home_slot(const flowkey::Key& k, uint32_t mask) { return (uint32_t)flowkey::key_hash(k) & mask; }
 
-// halo_pmflow_record_device's count / scan / scatter: frames per workgroup, and tiles per pass of
-// the one-workgroup scan (four per lane). arp_fwd.hip's gather has the same two.
+// halo_pmflow_record_device's count / scan / scatter: frames per workgroup, as arp_fwd.hip's gather
+// has them (the scan's pass is tile_scan.h's).
 constexpr uint32_t kRecordTile = 256;
-constexpr uint32_t kScanPass = 1024;
 
 struct Image {
     std::vector<Slot> slots;

@@ -18,13 +18,12 @@
 // reported as HALO_ROUTE_PANIC.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <mutex>
 #include <new>
 #include <shared_mutex>
 #include <vector>
 
-#include "halo_common.h"
+#include "device_table.h"
 #include "route_view.h"
 
 struct halo_route_table {
@@ -36,9 +35,6 @@ struct halo_route_table {
     std::vector<Node> nodes;  // nodes[0] = Root
     std::vector<halo_route_entry_t> routes;
     mutable std::mutex mu;  // RouteTable.Lock
-    // Device copies, double-buffered: lookups read gen[active]; a sync compiles into the other
-    // generation (after the device has drained every lookup that could still read it) and then
-    // publishes it, so a lookup in flight never sees a table being rewritten or freed.
     struct Gen {
         uint32_t* d_tbl24 = nullptr;
         uint32_t* d_tbl8 = nullptr;
@@ -47,14 +43,11 @@ struct halo_route_table {
         size_t lists_cap = 0;
         uint32_t* d_ids = nullptr;
         size_t ids_cap = 0;
-    } gen[2];
-    int device = -1;
-    std::atomic<int> active{-1};  // published generation, -1 before the first sync
-    std::mutex sync_mu;           // one sync at a time
-    // Lookups hold it shared from route_view until their kernel is enqueued (RouteViewLock); a sync
-    // holds it exclusively while it drains the device and rewrites the unpublished generation, so
-    // no lookup can be enqueued against a generation between its view and the drain.
-    mutable std::shared_mutex view_mu;
+    };
+    // The device copies; lookups hold dev.view_mu shared from route_view until their kernel is
+    // enqueued (RouteViewLock). dev.device is set by the first sync that allocated.
+    halo::Generations<Gen> dev;
+    std::mutex sync_mu;  // one sync at a time
 };
 
 namespace halo {
@@ -156,32 +149,6 @@ bool same_route(const halo_route_entry_t& a, const halo_route_entry_t& b) {
     return a.dst_ip == b.dst_ip && a.network_mask == b.network_mask && a.next_hop == b.next_hop && a.netif == b.netif;
 }
 
-template <typename T>
-int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return HALO_OK;
-    size_t c = cap ? cap : 256;
-    while (c < need) c *= 2;
-    T* q = nullptr;
-    if (hipMalloc(&q, c * sizeof(T)) != hipSuccess) return HALO_E_NOMEM;
-    if (p) (void)hipFree(p);
-    p = q;
-    cap = c;
-    return HALO_OK;
-}
-
-struct DeviceScope {  // run on `dev`, restore the caller's current device
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceScope() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 }  // namespace
 }  // namespace halo
 
@@ -196,11 +163,11 @@ extern "C" HALO_API int halo_route_table_create(halo_route_table_t** out) {
 
 extern "C" HALO_API int halo_route_table_destroy(halo_route_table_t* t) {
     if (!t) return HALO_E_INVAL;
-    if (t->device >= 0) {
-        halo::DeviceScope ds(t->device);
-        halo::ParkResidents park(t->device);  // through the frees: hipFree waits for every kernel
-        (void)halo::drain_device(t->device);  // no lookup may still read the tables
-        for (auto& g : t->gen) {
+    if (t->dev.device >= 0) {
+        halo::DeviceScope ds(t->dev.device);
+        halo::ParkResidents park(t->dev.device);  // through the frees: hipFree waits for every kernel
+        (void)halo::drain_device(t->dev.device);  // no lookup may still read the tables
+        for (auto& g : t->dev.gen) {
             if (g.d_tbl24) (void)hipFree(g.d_tbl24);
             if (g.d_tbl8) (void)hipFree(g.d_tbl8);
             if (g.d_lists) (void)hipFree(g.d_lists);
@@ -256,7 +223,7 @@ extern "C" HALO_API int halo_route_get(const halo_route_table_t* t, uint32_t id,
 
 extern "C" HALO_API int halo_route_sync_device(halo_route_table_t* t, int device) {
     if (!t || device < 0) return HALO_E_INVAL;
-    if (t->device >= 0 && t->device != device) return HALO_E_INVAL;  // one device per table
+    if (t->dev.device >= 0 && t->dev.device != device) return HALO_E_INVAL;  // one device per table
     int rc;
     {
         int cnt = 0;
@@ -273,16 +240,12 @@ extern "C" HALO_API int halo_route_sync_device(halo_route_table_t* t, int device
         c.walk(0, 0, 0, 0u);
     }
     std::lock_guard<std::mutex> sg(t->sync_mu);
-    std::unique_lock<std::shared_mutex> vl(t->view_mu);  // no lookup between its view and its launch
-    const int cur = t->active.load(std::memory_order_acquire);
-    // the generation written now was last published before `cur`: lookups launched while it was
-    // active may still be running on any stream of the device, so drain the device first
-    // (resident consumers are stopped for it, so a persistent ring's kernel cannot hold the write
-    // lock, and the lookups behind it, for its 20 ms idle window: ADVICE r3)
-    if (cur >= 0 && halo::drain_device(device) != HALO_OK) return HALO_E_HIP;
-    auto& g = t->gen[cur < 0 ? 0 : 1 - cur];
+    std::unique_lock<std::shared_mutex> vl(t->dev.view_mu);  // no lookup between its view and its launch
+    halo_route_table::Gen* gp = t->dev.begin_write();
+    if (!gp) return HALO_E_HIP;
+    auto& g = *gp;
     if (!g.d_tbl24 && hipMalloc(&g.d_tbl24, tbl24.size() * sizeof(uint32_t)) != hipSuccess) return HALO_E_NOMEM;
-    t->device = device;
+    t->dev.device = device;
     if ((rc = halo::grow(g.d_tbl8, g.tbl8_cap, tbl8.size() ? tbl8.size() : 1))) return rc;
     if ((rc = halo::grow(g.d_lists, g.lists_cap, lists.size() ? lists.size() : 1))) return rc;
     if ((rc = halo::grow(g.d_ids, g.ids_cap, ids.size() ? ids.size() : 1))) return rc;
@@ -293,27 +256,22 @@ extern "C" HALO_API int halo_route_sync_device(halo_route_table_t* t, int device
          hipMemcpy(g.d_lists, lists.data(), lists.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) ||
         (ids.size() && hipMemcpy(g.d_ids, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess))
         return HALO_E_HIP;
-    // hipMemcpy from pageable memory returns once the host buffer is consumed, not when the copy
-    // has landed: wait for it before publishing
-    if (halo::drain_device(device) != HALO_OK) return HALO_E_HIP;
-    t->active.store(cur < 0 ? 0 : 1 - cur, std::memory_order_release);
-    return HALO_OK;
+    return t->dev.publish();
 }
 
 namespace halo {
 RouteViewLock::RouteViewLock(const halo_route_table_t* t) : t_(t) {
-    if (t_) t_->view_mu.lock_shared();
+    if (t_) t_->dev.view_mu.lock_shared();
 }
 RouteViewLock::~RouteViewLock() {
-    if (t_) t_->view_mu.unlock_shared();
+    if (t_) t_->dev.view_mu.unlock_shared();
 }
 
 int route_view(const halo_route_table_t* t, LpmView* out) {
     if (!t || !out) return HALO_E_INVAL;
-    const int a = t->active.load(std::memory_order_acquire);
-    if (a < 0) return HALO_E_INVAL;  // never synced
-    const auto& g = t->gen[a];
-    *out = LpmView{g.d_tbl24, g.d_tbl8, g.d_lists, g.d_ids};
+    const halo_route_table::Gen* g = t->dev.published();
+    if (!g) return HALO_E_INVAL;  // never synced
+    *out = LpmView{g->d_tbl24, g->d_tbl8, g->d_lists, g->d_ids};
     return HALO_OK;
 }
 }  // namespace halo

@@ -33,8 +33,9 @@
 #include <new>
 #include <vector>
 
-#include "halo_common.h"
+#include "device_table.h"
 #include "switch_table.h"
+#include "tile_scan.h"
 
 namespace halo {
 namespace {
@@ -91,10 +92,6 @@ struct SwitchDevice {
     bool failed = false;  // a HIP call failed part-way: the device state is unknown
     int device = -1;
 };
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
 
 // The table slot holding `mac`, or -1 when its probe chain ends first.
 __device__ __forceinline__ int64_t table_find(const Slot* __restrict__ tab, uint32_t mask, uint64_t mac, uint32_t* port) {
@@ -160,79 +157,42 @@ __global__ void __launch_bounds__(kTile) sw_learn_kernel(const View v, const uin
 }
 
 __global__ void __launch_bounds__(kTile) sw_probe_kernel(const View v) {
-    __shared__ uint32_t s_new;
-    if (threadIdx.x == 0) s_new = 0;
-    __syncthreads();
     const uint32_t i = blockIdx.x * kTile + threadIdx.x;
-    bool is_new = false;
-    if (i < v.n) {
-        const uint32_t s = v.sref[i];
-        if (s != kNoSlot) {
-            Scratch* e = v.scratch + s;
-            if ((uint32_t)e->first == (uint32_t)~i) {  // this frame owns first[m]
-                uint32_t port = 0;
-                const int64_t slot = table_find(v.table, v.mask, e->key & kMacMask, &port);
-                is_new = slot < 0;
-                e->info = is_new ? 0u : (kHeld | (port & 0xFFu) << 8);
-                e->aux = is_new ? 0u : (uint32_t)slot;
-                v.sref[i] = s | kOwner | (is_new ? kNew : 0u);
+    tile_count(v.tiles, [&] {
+        bool is_new = false;
+        if (i < v.n) {
+            const uint32_t s = v.sref[i];
+            if (s != kNoSlot) {
+                Scratch* e = v.scratch + s;
+                if ((uint32_t)e->first == (uint32_t)~i) {  // this frame owns first[m]
+                    uint32_t port = 0;
+                    const int64_t slot = table_find(v.table, v.mask, e->key & kMacMask, &port);
+                    is_new = slot < 0;
+                    e->info = is_new ? 0u : (kHeld | (port & 0xFFu) << 8);
+                    e->aux = is_new ? 0u : (uint32_t)slot;
+                    v.sref[i] = s | kOwner | (is_new ? kNew : 0u);
+                }
             }
         }
-    }
-    const uint32_t c = (uint32_t)__popcll(__ballot(is_new));
-    if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&s_new, c);
-    __syncthreads();
-    if (threadIdx.x == 0) v.tiles[blockIdx.x] = s_new;
+        return is_new;
+    });
 }
 
 // One workgroup: tiles[t] becomes the number of new MACs in the tiles before t.
 __global__ void __launch_bounds__(256) sw_scan_kernel(const View v, uint32_t n_tiles) {
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_base;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_base = 0;
-    __syncthreads();
-    for (uint32_t t0 = 0; t0 < n_tiles; t0 += 1024) {  // four consecutive tiles per lane and pass
-        const uint32_t t = t0 + 4 * threadIdx.x;
-        uint32_t x[4], sum = 0;
-        for (uint32_t k = 0; k < 4; ++k) {
-            x[k] = t + k < n_tiles ? v.tiles[t + k] : 0u;
-            sum += x[k];
-        }
-        uint32_t inc = sum;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += y;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t before = s_base;
-        for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
-        uint32_t run = before + inc - sum;
-        for (uint32_t k = 0; k < 4; ++k) {
-            if (t + k < n_tiles) v.tiles[t + k] = run;
-            run += x[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == 255) s_base = before + inc;
-        __syncthreads();
-    }
+    const uint32_t fresh = scan_tiles(v.tiles, n_tiles);
     if (threadIdx.x == 0) {
-        const uint32_t room = v.capacity - v.state->entries, fresh = s_base;
+        const uint32_t room = v.capacity - v.state->entries;
         v.state->room = room;
         v.state->entries += fresh < room ? fresh : room;
     }
 }
 
 __global__ void __launch_bounds__(kTile) sw_admit_kernel(const View v) {
-    __shared__ uint32_t s_wave[kTile / 64];
     const uint32_t i = blockIdx.x * kTile + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t r = i < v.n ? v.sref[i] : kNoSlot;
     const bool owner = r != kNoSlot && (r & kOwner), is_new = owner && (r & kNew);
-    const uint64_t b = __ballot(is_new);
-    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
+    const uint64_t votes = tile_votes<kTile>(is_new);
     if (!owner) return;
     Scratch* e = v.scratch + (r & kSlotBits);
     const uint2 val = make_uint2(v.port, v.now);  // :92-94
@@ -240,8 +200,7 @@ __global__ void __launch_bounds__(kTile) sw_admit_kernel(const View v) {
         *reinterpret_cast<uint2*>(&v.table[e->aux].port) = val;
         return;
     }
-    uint32_t rank = v.tiles[blockIdx.x] + lanes_below(b);
-    for (uint32_t w = 0; w < wave; ++w) rank += s_wave[w];
+    const uint32_t rank = tile_rank<kTile>(votes, v.tiles[blockIdx.x]);
     if (rank >= v.state->room) return;  // MallocType fails from here on (:79-83); info stays 0
     const uint64_t mac = e->key & kMacMask;
     uint32_t s = sw::mac_hash(mac) & v.mask;
@@ -346,19 +305,6 @@ __global__ void __launch_bounds__(256) sw_rebuild_kernel(const Slot* __restrict_
     if ((threadIdx.x & 63u) == 0 && kept) atomicAdd(&state->survivors, kept);
 }
 
-struct DeviceScope {  // run on `dev`, restore the caller's current device
-    int prev = -1;
-    explicit DeviceScope(int dev) {
-        (void)hipGetDevice(&prev);
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceScope() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 SwitchDevice* dev_of(const halo_switch* s) { return static_cast<SwitchDevice*>(s->dev); }
 
 void free_all(SwitchDevice* d) {
@@ -372,14 +318,10 @@ void free_all(SwitchDevice* d) {
 }
 
 int ops_create(halo_switch* s) {
-    int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || s->cfg.device >= cnt) {
-        (void)hipGetLastError();
-        return HALO_E_NODEV;
-    }
-    DeviceScope ds(s->cfg.device);
-    int rc = check_device();
+    int rc = device_present(s->cfg.device);
     if (rc) return rc;
+    DeviceScope ds(s->cfg.device);
+    if ((rc = check_device())) return rc;
     SwitchDevice* d = new (std::nothrow) SwitchDevice;
     if (!d) return HALO_E_NOMEM;
     d->device = s->cfg.device;

@@ -24,13 +24,13 @@
 #include <hip/hip_runtime.h>
 
 #include "halo_common.h"
+#include "tile_scan.h"
 #include "tx_egress.h"
 
 namespace halo {
 namespace {
 
 using egress::kTile;
-constexpr uint32_t kScanPass = 1024;    // tiles per pass of the scan: four consecutive tiles per lane
 constexpr uint32_t kLanesPerRec = 16;   // lanes that copy one short record together (a wave per long one)
 constexpr uint32_t kSmallRecordDw = 32; // "short": two dwords per lane cover the record
 
@@ -70,10 +70,6 @@ __device__ __forceinline__ uint64_t frame_ports(const EgressParams& q, uint32_t 
     if (egress::sendable(*len, q.flags)) return m;
     *skip = true;
     return 0;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
 }
 
 template <uint32_t KIND>

@@ -19,6 +19,7 @@
 
 #include "arp_table.h"
 #include "halo_common.h"
+#include "tile_scan.h"
 #include "tx_respond.h"
 
 namespace halo {
@@ -30,8 +31,6 @@ using respond::Rec;
 using respond::Reply;
 
 static_assert(kTile == arp::kGatherTile, "the responders' tile is the gather's");
-constexpr uint32_t kScanPass = 1024;  // tiles per pass of the scan: four consecutive tiles per lane
-static_assert(kScanPass == 4 * 256, "four tiles per lane of the scan's one workgroup");
 static_assert(sizeof(halo_tx_build_desc_t) == 40 && sizeof(halo_respond_src_t) == 8 && sizeof(halo_tx_op_t) == 16 &&
                   sizeof(halo_rx_result_t) == 32,
               "layouts the kernels index by hand");
@@ -81,41 +80,8 @@ static_assert(HALO_RESPOND_KIND_COUNT == 4, "the tile total above names each kin
 
 // One workgroup: tiles[t] becomes the number of replies in the tiles before t; *count = all.
 __global__ void __launch_bounds__(256) respond_scan_kernel(uint32_t* tiles, uint32_t n_tiles, uint32_t* count) {
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t s_base;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_base = 0;
-    __syncthreads();
-    for (uint32_t t0 = 0; t0 < n_tiles; t0 += kScanPass) {
-        const uint32_t t = t0 + 4 * threadIdx.x;
-        uint32_t x[4], sum = 0;
-        for (uint32_t k = 0; k < 4; ++k) {
-            x[k] = t + k < n_tiles ? tiles[t + k] : 0u;
-            sum += x[k];
-        }
-        uint32_t inc = sum;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += y;
-        }
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t before = s_base;
-        for (uint32_t w = 0; w < wave; ++w) before += s_wave[w];
-        uint32_t run = before + inc - sum;
-        for (uint32_t k = 0; k < 4; ++k) {
-            if (t + k < n_tiles) tiles[t + k] = run;
-            run += x[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == 255) s_base = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = s_base;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+    const uint32_t total = scan_tiles(tiles, n_tiles);
+    if (threadIdx.x == 0) *count = total;
 }
 
 __global__ void __launch_bounds__(kTile) respond_scatter_kernel(const Args a, const uint32_t* __restrict__ offsets_dw,
@@ -124,19 +90,14 @@ __global__ void __launch_bounds__(kTile) respond_scatter_kernel(const Args a, co
                                                                 halo_tx_build_desc_t* __restrict__ desc,
                                                                 halo_respond_src_t* __restrict__ src,
                                                                 uint32_t* __restrict__ dst_ip, uint32_t cap) {
-    __shared__ uint32_t s_wave[kTile / 64];
     const uint32_t i = blockIdx.x * kTile + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     Reply o;
     o.kind = kNone;
     if (i < a.n) o = reply_of(a, i, lens[i], offsets_dw[i]);
     const bool sel = o.kind != kNone;
-    const uint64_t b = __ballot(sel);
-    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
+    const uint64_t votes = tile_votes<kTile>(sel);
     if (!sel) return;
-    uint32_t rank = tiles[blockIdx.x] + lanes_below(b);
-    for (uint32_t w = 0; w < wave; ++w) rank += s_wave[w];
+    const uint32_t rank = tile_rank<kTile>(votes, tiles[blockIdx.x]);
     if (rank >= cap) return;
     uint2* d = reinterpret_cast<uint2*>(desc + rank);
     d[0] = make_uint2((uint32_t)o.payload_off, (uint32_t)(o.payload_off >> 32));

@@ -95,8 +95,13 @@ def read_constants() -> dict:
     blocks = 1
     for f in kmax.split("*"):
         blocks *= int(re.fullmatch(r"\s*(\d+)(?:ull|u)?\s*", f).group(1))
+    # egress_scan_kernel keeps its own fused loop and takes its pass from tile_scan.h
+    with open(os.path.join(CSRC, "tile_scan.h")) as fh:
+        tile = fh.read()
+    assert '#include "tile_scan.h"' in hip and "kScanPass =" not in hip
+    assert _one(r"t0 < n_tiles; t0 \+= (\w+),", hip) == "kScanPass"
     return {"kTile": int(_one(r"constexpr uint32_t kTile = (\d+);", hdr)),
-            "kScanPass": int(_one(r"constexpr uint32_t kScanPass = (\d+);", hip)),
+            "kScanPass": int(_one(r"constexpr uint32_t kScanPass = (\d+);", tile)),
             "egress_blocks": blocks}
 
 

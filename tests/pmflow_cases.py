@@ -126,10 +126,11 @@ def read_constants() -> dict:
         arp = fh.read()
     # one workgroup per tile in both tile kernels: no grid cap, so no further edge
     assert len(re.findall(r"dim3\(n_tiles\), dim3\(kRecordTile\)", hip)) == 2
-    assert _one(r"t0 < n_tiles; t0 \+= (\w+)\)", hip) == "kScanPass"
     assert "static_assert(kRecordTile == arp::kGatherTile" in hip
+    from tests import scale_cases as S
+
     return {"kRecordTile": int(_one(r"constexpr uint32_t kRecordTile = (\d+);", hdr)),
-            "kScanPass": int(_one(r"constexpr uint32_t kScanPass = (\d+);", hdr)),
+            "kScanPass": S.scan_pass("pmflow_fwd.hip", "pmflow_scan_kernel"),
             "kGatherTile": int(_one(r"constexpr uint32_t kGatherTile = (\d+);", arp))}
 
 

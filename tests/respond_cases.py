@@ -203,9 +203,10 @@ def read_constants() -> dict:
         hdr = fh.read()
     # one workgroup per tile in both tile kernels: no grid cap, so no further edge
     assert len(re.findall(r"dim3\(n_tiles\), dim3\(kTile\)", hip)) == 2 and "kMax" not in hip
-    assert _one(r"t0 < n_tiles; t0 \+= (\w+)\)", hip) == "kScanPass"
+    from tests import scale_cases as S
+
     return {"kTile": int(_one(r"constexpr uint32_t kTile = (\d+);", hdr)),
-            "kScanPass": int(_one(r"constexpr uint32_t kScanPass = (\d+);", hip))}
+            "kScanPass": S.scan_pass("tx_respond.hip", "respond_scan_kernel")}
 
 
 def derived(c: dict) -> dict:

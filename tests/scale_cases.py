@@ -113,6 +113,16 @@ def _one(pattern: str, text: str, flags=0) -> str:
     return found[0]
 
 
+def scan_pass(hip: str, kernel: str) -> int:
+    """The tiles per pass of `kernel`'s one-workgroup scan: the kernel of file `hip` calls
+    scan_tiles, and scan_tiles' one loop (tile_scan.h) advances by the one kScanPass."""
+    hdr, text = _src("tile_scan.h"), _src(hip)
+    _one(r"__global__ void __launch_bounds__\(256\) %s\([^)]*\) \{\s*const uint32_t \w+ = scan_tiles\(" % kernel, text)
+    assert len(re.findall(r"scan_tiles\(", text)) == 1 and "t0 +=" not in text, hip  # no scan loop of the file's own
+    assert _one(r"t0 < n_tiles; t0 \+= (\w+)\)", hdr) == "kScanPass"
+    return int(_one(r"constexpr uint32_t kScanPass = (\d+);", hdr))
+
+
 def read_constants() -> dict:
     """The named constants of the launch code, as the sources have them now."""
     arp, sw, nat = _src("arp_fwd.hip"), _src("switch_fwd.hip"), _src("nat_lookup.hip")
@@ -148,8 +158,8 @@ def read_constants() -> dict:
         "tx_waves": _product(_one(r"const uint64_t kMaxBlocks = ([^;/]+)/ wpb;", tx)),
         "sw_resolve_cap": int(resolve[0]),
         "sw_rebuild_cap": int(rebuild[0]),
-        "arp_pass": int(_one(r"t0 \+= (\d+)\)", arp)),
-        "sw_pass": int(_one(r"t0 \+= (\d+)\)", sw)),
+        "arp_pass": scan_pass("arp_fwd.hip", "arp_scan_kernel"),
+        "sw_pass": scan_pass("switch_fwd.hip", "sw_scan_kernel"),
         "kTile": int(_one(r"constexpr uint32_t kTile = (\d+);", sw)),
         "kGatherTile": int(_one(r"constexpr uint32_t kGatherTile = (\d+);", arp_h)),
         "kShortScan": int(_one(r"#define HALO_XXH3_SHORT_SCAN (\d+)", fh)),

@@ -222,6 +222,62 @@ def test_generations(dev):
         p.close()
 
 
+def test_route_array_grows_under_a_queued_encap(dev):
+    """The route array of a generation starts at 256 entries. A sync with 300 routes follows an encap
+    that nothing waited for, and a second sync then reallocates the array of the generation written
+    first, while the other one is published. Both encaps, 65 frames each (a wave and a lane), give
+    the model's results; the second has route ids on both sides of 256."""
+    import torch
+
+    from halo_amd._lib import ARP_RESULT_DTYPE
+    from halo_amd.route import RouteTable
+
+    n, in_netif = 65, 1
+    p, rt = K.Pair(capacity=8), RouteTable(0)
+    try:
+        hosts = [0x0A000010 + k for k in range(4)]  # neighbours of NetIf 0
+        for k, ip in enumerate(hosts):
+            p.set(0, ip, K.mac(20 + k), 1000)
+        rt.AddRoute(RouteTable.entry(0x0A000000, 0xFFFFFF00, 0, 0))       # id 0: direct
+        rt.AddRoute(RouteTable.entry(NH_HIT, 0xFFFF0000, hosts[1], 0))    # id 1: through a neighbour
+        p.t.sync(rt)
+        rng = np.random.default_rng(65)
+
+        def encap(rids):
+            """Queues the L2 step; returns the tensors (kept allocated) and the model's answer."""
+            frames = [_ipv4_frame(rng, 60 + i % 6, hosts[i % 4] if i % 3 else _absent([(0, h) for h in hosts], 0, i)) for i in range(n)]
+            data, offs, lens = _pack(rng, frames)
+            want, want_res = data.copy(), np.zeros(n, ARP_RESULT_DTYPE)
+            for i, f in enumerate(frames):
+                v, out, tx, target, after = p.m.encap(f, _route_of(rt, int(rids[i])), in_netif, True)
+                want_res[i] = (v, out, tx, target)
+                want[4 * int(offs[i]):4 * int(offs[i]) + len(f)] = np.frombuffer(after, np.uint8)
+            d, o, ln = _up(dev, data, offs, lens)
+            d_rids = torch.from_numpy(rids.view(np.int32)).to(dev)
+            res, counts, miss = p.t.encap(d, o, ln, d_rids, in_netif)
+            return (d, o, ln, d_rids, res, counts, miss), want, want_res
+
+        first = encap(np.array([i % 2 for i in range(n)], np.uint32))  # queued; nothing waits for it before the sync
+        for k in range(2, 300):  # next hops that are neighbours of NetIf 0, on NetIf 0 and on one that does not hold them
+            assert rt.AddRoute(RouteTable.entry(0x0B000000 + (k << 8), 0xFFFFFF00, hosts[k % 4] if k % 2 else 0, 0 if k % 5 else 2)) == k
+        p.t.sync(rt)
+        p.t.sync(rt)
+        second = encap(np.array([(0, 1, 255, 256, 257, 299, 258, 2)[i % 8] for i in range(n)], np.uint32))
+        torch.cuda.synchronize()
+        for (t, want, want_res), verdicts in ((first, {M.HIT, M.MISS}), (second, {M.HIT, M.MISS})):
+            got_res = t[4].cpu().numpy().reshape(-1).view(ARP_RESULT_DTYPE)
+            bad = np.nonzero(got_res != want_res)[0]
+            assert bad.size == 0, [(int(i), got_res[i], want_res[i]) for i in bad[:5]]
+            assert np.array_equal(t[0].cpu().numpy(), want)
+            assert list(t[5].cpu().numpy()) == [int((want_res["verdict"] == v).sum()) for v in range(7)]
+            assert verdicts <= set(want_res["verdict"].tolist())
+        hit_ids = {int(r) for r, v in zip(second[0][3].cpu().numpy(), second[2]["verdict"]) if v == M.HIT}
+        assert {0, 1, 257, 299} <= hit_ids and 255 not in hit_ids  # resolved through the old and the new part of the array
+    finally:
+        p.close()
+        rt.close()
+
+
 def _arp_frame(rng, dst, src, nif, length=60, op=None):
     m = K.NETIFS[nif]
     op = int(rng.choice([1, 1, 2, 3])) if op is None else op

@@ -230,6 +230,84 @@ def _records(n):
     return r
 
 
+def test_generations_grow_under_queued_lookups(dev):
+    """Three writes of the device copy around lookups nothing waits for: a sync of 3 flows; a lookup;
+    197 more flows and a sync, whose slot array no longer fits the first allocation (256 slots); a
+    lookup that hits three flows in four; an expiry tick, which folds the device's stamps, removes
+    the flows never hit and publishes into the generation written first, reallocating it while the
+    other one is published; a lookup without a sync. One synchronise at the end: every lookup is the
+    model's at its own table state, and the survivors carry the stamps the device wrote."""
+    import torch
+
+    from halo_amd import PortMappingFlowTable
+    from halo_amd._lib import PMFLOW_VIA_DTYPE, TX_OP_DTYPE
+
+    n_flows, T = 200, 5000
+    rng = np.random.RandomState(77)
+    items = []
+    while len(items) < n_flows:
+        it = (int(rng.randint(1, 1 << 31)), int(rng.randint(1, 65536)), C.SERVER + int(rng.randint(0, 4)),
+              int(rng.randint(1, 65536)), int(rng.choice([6, 17])), int(rng.randint(1, 65536)))
+        if it[:5] not in {x[:5] for x in items}:
+            items.append(it)
+    recs = _records(n_flows + 8)  # every flow's reply from the LAN host, then eight records of no flow
+    recs["src_ip"], recs["sport"], recs["dst_ip"], recs["dport"] = C.SERVER + 9, 1000, 0x08080808, 53
+    for i, it in enumerate(items):
+        recs[i]["dst_ip"], recs[i]["dport"], recs[i]["src_ip"], recs[i]["sport"], recs[i]["ip_proto"] = it[:5]
+    rt, ids = _routes()
+    cycle = [ids["via_wan2"], ids["default"], AM.ROUTE_NONE, ids["lan"], 1000, ids["wan2"], AM.ROUTE_PANIC_ID]
+    rids = np.array([cycle[i % len(cycle)] for i in range(len(recs))], np.uint32)
+    t, m = PortMappingFlowTable(C.lib_netifs(), C.GATEWAYS, 400), PM.Model(C.model_netifs(), C.GATEWAYS, 400)
+
+    def record(nif, part, now):
+        dropped, added = t.record(nif, C.item_array(part), now)
+        assert added == len(part) == m.record(nif, part, now)[1] and not dropped.any()
+
+    def lookup(which, now):
+        """Queues a lookup of the records `which`: its tensors and the model's answer at this state."""
+        r, rd = recs[which], rids[which]
+        want_via, want_ops = np.zeros(len(r), PMFLOW_VIA_DTYPE), np.zeros(len(r), TX_OP_DTYPE)
+        for i in range(len(r)):
+            tup = tuple(int(r[i][k]) for k in ("ip_proto", "src_ip", "dst_ip", "sport", "dport"))
+            v, wan, port, hop, snat = m.lookup(tup, _route_arg(rt, rd[i]), now)
+            want_via[i] = (v, wan, port, hop)
+            if snat is not None:
+                want_ops[i]["steps"], want_ops[i]["src_ip"], want_ops[i]["src_port"] = TX_NAT_SRC, snat[0], snat[1]
+        d_recs, d_rids = _t(dev, r.view(np.uint8).reshape(-1, 32)), _t(dev, rd.view(np.int32))
+        return (d_recs, d_rids) + t.lookup(d_recs, now, d_rids), want_via, want_ops
+
+    try:
+        record(C.WAN2, items[:3], T)
+        t.sync(rt)
+        every = np.arange(len(recs))
+        calls = [lookup(every, T + 1)]  # queued; nothing waits for it before the sync
+        record(C.WAN2, items[3:100], T)
+        record(C.DMZ, items[100:], T)
+        assert int(t.layout_stats()["slots"]) > 256
+        t.sync(rt)
+        calls.append(lookup(every[every % 4 != 3], T + 50))
+        removed = t.TableClear(T + 70)
+        assert removed == m.expire(T + 70) and 0 < removed < n_flows - 3
+        assert int(t.layout_stats()["slots"]) > 256  # the generation written first has to grow as well
+        calls.append(lookup(every, T + 71))
+        torch.cuda.synchronize()
+        for k, ((_, _, ops, via, hit, counts), want_via, want_ops) in enumerate(calls):
+            got_via = via.cpu().numpy().reshape(-1).view(PMFLOW_VIA_DTYPE)
+            bad = np.nonzero(got_via != want_via)[0]
+            assert bad.size == 0, (k, [(int(i), got_via[i], want_via[i]) for i in bad[:5]])
+            assert np.array_equal(hit.cpu().numpy(), (want_via["verdict"] >= PM.V_HIT).astype(np.uint8)), k
+            assert ops.cpu().numpy().tobytes() == want_ops.tobytes(), k
+            assert list(counts.cpu().numpy()) == [int((want_via["verdict"] == v).sum()) for v in range(4)], k
+        hits = [int((w["verdict"] >= PM.V_HIT).sum()) for _, w, _ in calls]
+        assert hits[0] == 3 and hits[1] == 150 and hits[2] == n_flows - removed == 150
+        assert t.TableClear(T + 71) == 0 == m.expire(T + 71)  # folds the third lookup's stamps
+        assert C.listing_of(t.List()) == m.listing()
+        assert {e[8] for e in m.listing()} == {T + 71}
+    finally:
+        t.close()
+        rt.close()
+
+
 def _record_inputs(items, n, cand_at):
     """Synthetic inputs of halo_pmflow_record_device for frames WAN2 received: records, inbound
     verdicts, ops and ARP results, with the candidates at `cand_at` cycling through known-identical,
