@@ -180,6 +180,12 @@ RING_STOP_NAMES = ("EMPTY", "BAD_LEN", "PARTIAL", "CAPACITY", "MAX", "BAD_CURSOR
 RING_STOP = {name: code for code, name in enumerate(RING_STOP_NAMES)}
 RING_REGISTER = 0x1
 RING_PERSISTENT = 0x2  # HALO_RING_PERSISTENT: small polls served by a resident consumer kernel
+# the tx ring producer: halo_tx_ring_result_t (24 bytes), HALO_TXRING_*
+TXRING_RESULT_DTYPE = np.dtype([("status", "<u4"), ("records", "<u4"), ("bytes", "<u8"), ("head", "<u8")])
+assert TXRING_RESULT_DTYPE.itemsize == 24
+TXRING_STATUS_NAMES = ("OK", "SHORT", "BAD_SPAN")
+TXRING_OK, TXRING_SHORT, TXRING_BAD_SPAN = 0, 1, 2
+TXRING_MAX_RECORD = 16376
 
 def host_array(shape, dtype=np.uint8) -> np.ndarray:
     """A zeroed host array on pages of its own: an anonymous mmap, page-aligned, its size rounded
@@ -458,6 +464,13 @@ _PROTOS = {
         ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
     "halo_ring_write_span": (ctypes.c_int, [
         ctypes.c_void_p, _u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)]),
+    "halo_tx_ring_attach": (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]),
+    "halo_tx_ring_detach": (ctypes.c_int, [ctypes.c_void_p]),
+    "halo_tx_ring_workspace": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "halo_tx_ring_write_span_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, ctypes.c_uint64, _u8p, _u8p, ctypes.c_uint64, ctypes.c_void_p]),
+    "halo_tx_ring_debug_copy_mode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
     "halo_tx_egress_workspace": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
     "halo_tx_egress_masks_device": (ctypes.c_int, [
         ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64,

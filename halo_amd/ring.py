@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (RESULT_DTYPE, RING_HEADER, RING_PERSISTENT, RING_REGISTER, RING_SCAN_DTYPE, RING_STATS_DTYPE,
-                   RING_STOP_NAMES, NetIf)
+                   RING_STOP_NAMES, TXRING_RESULT_DTYPE, NetIf)
 from .protocol import flags_word
 
 WIRE_MAX_PACKET_SIZE = 1514  # engine/engine.go:507
@@ -165,6 +165,104 @@ class RingConsumer:
         st = np.zeros(1, RING_STATS_DTYPE)
         _lib.check("halo_rx_ring_get_stats", _lib.lib.halo_rx_ring_get_stats(self._h, st.ctypes.data))
         return {k: int(st[k][0]) for k in RING_STATS_DTYPE.names}
+
+
+class RingProducer:
+    """The GPU producer of one ring (halo_tx_ring_attach): ``halo_ring_write_span`` with the span in
+    device memory. The device finds the records, reads head and tail, copies what fits into the
+    mapped ring and publishes head; the host reads a 24-byte result. ``register=False`` attaches to a
+    ring that is already mapped for the device (one a ``RingConsumer`` registered): close the
+    producer before that registration goes away. One producer per ring; its writes go to one stream."""
+
+    def __init__(self, ring: RingBuffer, device: int = 0, register: bool = True):
+        self.ring, self.device = ring, device
+        self._ws = None
+        self._retired = []  # outgrown workspaces, kept until close(): earlier writes may still be queued on them
+        h = ctypes.c_void_p()
+        rc = _lib.lib.halo_tx_ring_attach(device, ring.mem.ctypes.data, 0, RING_REGISTER if register else 0,
+                                          ctypes.byref(h))
+        if rc == _lib.HALO_E_HIP and register:
+            _lib._leaked.append(ring)  # its pages may still be pinned for the device: never free them
+        _lib.check("halo_tx_ring_attach", rc)
+        self._h = h
+
+    def close(self):
+        """Wait for the device's work on the ring and detach. Raises HaloError if the ring could not
+        be unregistered: its pages then stay mapped for the device, so the ring is never freed."""
+        if getattr(self, "_h", None):
+            rc = _lib.lib.halo_tx_ring_detach(self._h)
+            self._h = None
+            self._ws, self._retired = None, []
+            if rc != _lib.HALO_OK:
+                _lib._leaked.append(self.ring)
+                _lib.check("halo_tx_ring_detach", rc)
+
+    def __del__(self):
+        self.close()
+
+    @staticmethod
+    def workspace_bytes(span_bytes: int) -> int:
+        return int(_lib.lib.halo_tx_ring_workspace(span_bytes))
+
+    def _workspace(self, span_bytes: int, dev):
+        import torch
+
+        need = self.workspace_bytes(span_bytes)
+        if need == 0:
+            raise _lib.HaloError("halo_tx_ring_workspace", _lib.HALO_E_INVAL)
+        if self._ws is None or self._ws.numel() < need:
+            if self._ws is not None:
+                self._retired.append(self._ws)
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self._ws
+
+    def write_span_async(self, d_span, span_bytes: int | None = None, stream=None, result=None, workspace=None):
+        """Enqueue the write of ``d_span[:span_bytes]`` (a cuda uint8 tensor of whole records, 4-byte
+        aligned) and return the result tensor (uint8 [24] on the device, ``TXRING_RESULT_DTYPE``
+        once the stream has reached it). No synchronisation; writes on one stream chain."""
+        import torch
+
+        n = int(d_span.numel() if span_bytes is None else span_bytes)
+        if result is None:
+            result = torch.empty(24, dtype=torch.uint8, device=d_span.device)
+        ws = workspace if workspace is not None else self._workspace(n, d_span.device)
+        st = (stream if stream is not None else torch.cuda.current_stream()).cuda_stream
+        rc = _lib.lib.halo_tx_ring_write_span_device(self._h, _lib.ptr(d_span), n, _lib.ptr(result), _lib.ptr(ws),
+                                                     ws.numel() * ws.element_size(), st)
+        _lib.check("halo_tx_ring_write_span_device", rc)
+        return result
+
+    @staticmethod
+    def read_result(result) -> np.ndarray:
+        """A result tensor as one TXRING_RESULT_DTYPE record (synchronises)."""
+        return result.cpu().numpy().view(TXRING_RESULT_DTYPE)[0]
+
+    def write_span(self, d_span, span_bytes: int | None = None, stream=None):
+        """The synchronous convenience: enqueue, synchronise, read the result — (status, records
+        taken, bytes taken). After ``TXRING_SHORT`` resubmit ``d_span[bytes:]``."""
+        import torch
+
+        res = self.write_span_async(d_span, span_bytes, stream)
+        (stream if stream is not None else torch.cuda.current_stream()).synchronize()
+        r = self.read_result(res)
+        return int(r["status"]), int(r["records"]), int(r["bytes"])
+
+
+def publish_egress(result, producers, stream=None):
+    """Publish every port's stream of a device ``EgressResult`` into its tx ring: one
+    ``write_span_async`` per port on ``stream``, then one synchronisation. Returns one
+    TXRING_RESULT_DTYPE record per port; after ``TXRING_SHORT`` the caller resubmits
+    ``result.device_stream(p)[bytes:]``. Reads the port summaries (a synchronisation of its own:
+    span_bytes is a host value)."""
+    import torch
+
+    if len(producers) != result.n_ports:
+        raise ValueError("one producer per egress port")
+    ports = result.ports
+    res = [prod.write_span_async(result.device_stream(p), int(ports[p]["bytes_written"]), stream)
+           for p, prod in enumerate(producers)]
+    (stream if stream is not None else torch.cuda.current_stream()).synchronize()
+    return np.array([RingProducer.read_result(r) for r in res], TXRING_RESULT_DTYPE)
 
 
 class Wire:

@@ -1412,6 +1412,81 @@ HALO_API int halo_tx_egress_host(const halo_egress_config_t* cfg, uint32_t kind,
 HALO_API int halo_ring_write_span(void* ring_memory, const uint8_t* span, uint64_t span_bytes,
                                   uint32_t* records_written, uint64_t* bytes_written);
 
+/* ---- the tx ring producer: halo_ring_write_span from device memory ---------------------------
+ * An egress stream (halo_tx_egress_*_device) is published into its tx ring where it lies in HBM:
+ * the device finds the record boundaries, reads head and tail, copies the records that fit into the
+ * mapped ring and publishes head. The host touches no frame byte and learns the outcome from a
+ * 24-byte result. halo_ring_write_span stays the call for polls at the reference's cadence.
+ *
+ * ATTACH as the ring's producer. The header is validated as halo_rx_ring_attach and
+ * halo_ring_write_span validate it (layout version, size and mask, head - tail <= size, 4-byte
+ * cursors, `offset`), before any device call. With HALO_RING_REGISTER the ring is registered as an
+ * rx ring is (page rules and HALO_E_INVAL answers of halo_rx_ring_attach; detach unregisters).
+ * Without it the ring memory must already be mapped for the device in one piece (a live
+ * registration of this library, e.g. the same ring attached by halo_rx_ring_attach with
+ * HALO_RING_REGISTER, or pinned memory), else HALO_E_INVAL: one registration then carries a device
+ * producer and a device consumer. HALO_RING_PERSISTENT and unknown flags: HALO_E_INVAL. HALO_E_HIP
+ * from an attach with HALO_RING_REGISTER: the ring's pages may still be pinned, keep it allocated.
+ *
+ * WRITE a span: asynchronous on `stream`, no host round trip. d_span is device memory, 4-byte
+ * aligned; span_bytes is a host value, a multiple of 4 (halo_egress_port_t.bytes_written). What
+ * happens is what halo_ring_write_span does for the same ring state and span:
+ *   1. every record header of the examined window is checked before a ring byte is written: a
+ *      length of 0, a length above size / 2, or a record running past the span's end gives
+ *      status = HALO_TXRING_BAD_SPAN (the host call's HALO_E_INVAL), nothing written, head unchanged;
+ *   2. room = size - (head - tail), read on the device (tail: a system-scope acquire load); 0 when
+ *      head - tail > size or tail & 3;
+ *   3. the longest prefix of whole records with total size <= room is taken: status =
+ *      HALO_TXRING_OK when that is the whole span, else HALO_TXRING_SHORT (possibly 0 records);
+ *      `records` and `bytes` say what was taken, so the caller resubmits d_span + bytes;
+ *   4. the prefix is copied to data[(head + k) & mask] — the ring bytes halo_ring_write_span leaves;
+ *   5. head + bytes is published once, after every copied byte, by a system-scope release store,
+ *      only when bytes > 0. tail and the rest of the header are never written;
+ *   6. *d_result (optional; device or mapped host memory, 8-byte aligned) is written in stream order.
+ * Nothing on the device waits: a full ring is answered with SHORT.
+ *
+ * BUILD-DEFINED DIFFERENCES from the host call:
+ *   - only the first min(span_bytes, size) bytes are examined: no record beyond them is taken, a
+ *     malformed record beyond them is not seen, and a record cut by that window is not an error;
+ *   - a record longer than HALO_TXRING_MAX_RECORD (16,376) bytes is BAD_SPAN (the device record
+ *     walk's capacity); the host accepts records up to size / 2;
+ *   - span_bytes above what halo_rx_ring_scan_workspace accepts is HALO_E_INVAL
+ *     (halo_tx_ring_workspace returns 0 for it);
+ *   - span_bytes == 0 is OK and still writes the result: OK, 0, 0, head.
+ *
+ * ORDERING: one producer per ring. Calls on one stream chain without the host knowing head: each
+ * reads it from the ring after the previous call's publish. Calls on two streams for one ring are
+ * the caller's error. A host halo_ring_write_* on the same ring is legal once the stream is
+ * synchronised. d_workspace (halo_tx_ring_workspace(span_bytes) bytes, 16-byte aligned) serves any
+ * number of calls issued on one stream. The ring memory must stay mapped until detach returns.
+ *
+ * Argument checks come before a device is looked for. HALO_E_INVAL: a null handle; d_span null or
+ * not 4-byte aligned with span_bytes > 0; span_bytes & 3; d_result not 8-byte aligned; d_workspace
+ * null or not 16-byte aligned; workspace_bytes < halo_tx_ring_workspace(span_bytes) (which is never
+ * 0 for a span it accepts). Then HALO_E_NODEV / _ARCH as elsewhere. */
+#define HALO_TXRING_OK 0u       /* the whole span was taken                                     */
+#define HALO_TXRING_SHORT 1u    /* a proper prefix (possibly nothing) was taken: the ring is full */
+#define HALO_TXRING_BAD_SPAN 2u /* a malformed record in the examined window: nothing written   */
+#define HALO_TXRING_MAX_RECORD 16376u
+typedef struct halo_tx_ring_result {
+    uint32_t status;  /* HALO_TXRING_*                       */
+    uint32_t records; /* records taken                        */
+    uint64_t bytes;   /* their bytes: a whole number of records */
+    uint64_t head;    /* the ring's head after the call       */
+} halo_tx_ring_result_t; /* 24 B */
+typedef struct halo_tx_ring halo_tx_ring_t;
+HALO_API int halo_tx_ring_attach(int device, void* ring_mem, int64_t offset, uint32_t attach_flags,
+                                 halo_tx_ring_t** out);
+/* Waits for the device's work on the ring and frees the handle. HALO_E_HIP: the ring memory could
+ * not be unregistered (keep it allocated: its pages stay mapped for the device). */
+HALO_API int halo_tx_ring_detach(halo_tx_ring_t* ring);
+/* Bytes of device workspace a write of span_bytes needs; 0 for a span that is too large. Never
+ * decreases with span_bytes. */
+HALO_API uint64_t halo_tx_ring_workspace(uint64_t span_bytes);
+HALO_API int halo_tx_ring_write_span_device(halo_tx_ring_t* ring, const uint8_t* d_span, uint64_t span_bytes,
+                                            halo_tx_ring_result_t* d_result, void* d_workspace,
+                                            uint64_t workspace_bytes, halo_stream_t stream);
+
 /* ---- the reference engine's per-frame decision (engine/ethernet_engine.go:13-31,
  *      engine/ipv4_engine.go:18-47, engine/{udp,tcp,icmp}_engine.go) ------------------ */
 typedef enum halo_rx_action {
