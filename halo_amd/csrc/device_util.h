@@ -60,7 +60,8 @@ __device__ __forceinline__ uint32_t group_sum(uint32_t x) {
 typedef const __attribute__((address_space(1))) uint32_t gu32;
 
 // load4 with a non-temporal hint on the 16-byte path (bytes read once: not kept in the L2 ahead
-// of lines another group will read)
+// of lines another group will read). Only the 16-lane groups' later rounds take it (rx_parse.hip,
+// kLaterNtG); tried: every load4 non-temporal (in git history up to 9ac2a89).
 __device__ __forceinline__ void load4_nt(const uint8_t* frame, uint32_t d0, uint32_t ndw, uint32_t (&w)[4]) {
     gu32* p = (gu32*)(reinterpret_cast<const uint32_t*>(frame) + d0);
     if (d0 + 4 <= ndw) {
@@ -76,11 +77,7 @@ __device__ __forceinline__ void load4(const uint8_t* frame, uint32_t d0, uint32_
     gu32* p = (gu32*)(reinterpret_cast<const uint32_t*>(frame) + d0);
     if (d0 + 4 <= ndw) {
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));  // 4-byte aligned 16 B
-#if HALO_RX_NT_LOADS
-        const u32x4 v = __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4*)p);
-#else
         const u32x4 v = *(const __attribute__((address_space(1))) u32x4*)p;
-#endif
         w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
     } else {
 #pragma unroll
@@ -92,11 +89,7 @@ __device__ __forceinline__ void load4(const uint8_t* frame, uint32_t d0, uint32_
 __device__ __forceinline__ void load4_inside(const uint8_t* frame, uint32_t d0, uint32_t (&w)[4]) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
     gu32* p = (gu32*)(reinterpret_cast<const uint32_t*>(frame) + d0);
-#if HALO_RX_NT_LOADS
-    const u32x4 v = __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4*)p);
-#else
     const u32x4 v = *(const __attribute__((address_space(1))) u32x4*)p;
-#endif
     w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
 }
 

@@ -3,26 +3,22 @@
 // strings, and the NAT flow-table keys of the forward path (NatFlowHash / NatWanFlowHash,
 // engine/ipv4_engine.go:451-479) hashed straight from parsed rx records.
 //
-// Shape. Short strings (<= 240 B: hashSmall / hashMedium / hashLarge, xxh3.go:59-129) are one
-// lane each. Long strings (hashLong, :132-209) are the 8-accumulator stripe loop, which maps
-// onto 8 lanes: lane j of a group owns accumulator j, reads bytes [8j, 8j+8) of each 64-byte
-// stripe (the group's load is one coalesced 64-byte access) and gets input word j^1 from its
-// neighbour with a DPP quad_perm swap; the merge folds lane pairs the same way. Two kernels on
-// one stream: short strings lane-per-string, then long strings — each wave scans 64 strings and
-// takes its long ones eight at a time (one per 8-lane group), so ragged batches keep every lane
-// busy and neither path pays the other's register budget.
+// Shape. One kernel, the run kernel (xxh3_run_kernel below): a one-wave block owns a window of
+// kRunWin consecutive strings and splits it into 16 contiguous runs, one per 4-lane group. Lane j
+// of a group owns accumulators 2j and 2j+1 of hashLong's eight (xxh3.go:132-209) and reads bytes
+// [16j, 16j+16) of each 64-byte stripe, so accumulateStripe's i ^ 1 exchange stays inside the
+// lane; strings of 17..240 B (hashMedium / hashLarge, :94-129) put their mix16 terms on the same
+// four lanes and the same loads, strings of <= 16 B take hashSmall (:59-91). The window's hashes
+// leave as whole lines in string order.
 //
-// Data are read as aligned dwords merged with v_alignbyte: any byte offset works, and no read
-// touches a dword that holds none of the string's bytes (so never a page the string is not on).
+// String data are read 16 bytes at a time at any byte address, every byte a string byte; the
+// <= 16 B path reads aligned dwords merged with v_alignbyte. Either way no read touches a dword
+// that holds none of the string's bytes (so never a page the string is not on).
 #include <hip/hip_runtime.h>
 
 #include "device_util.h"
 #include "flow_key.h"
 #include "halo_common.h"
-
-#ifndef HALO_XXH3_FUSED_SHORT
-#define HALO_XXH3_FUSED_SHORT 1  // the long kernel also hashes its windows' short strings (no short launch)
-#endif
 
 namespace halo {
 namespace {
@@ -94,9 +90,6 @@ __device__ __forceinline__ uint64_t rrmxmx(uint64_t v, uint64_t len) {  // xxh3.
     v ^= v >> 28;
     return v;
 }
-[[maybe_unused]] __device__ __forceinline__ uint64_t mix16(const uint8_t* d, uint32_t doff, uint32_t soff) {  // :221-225
-    return mul_fold64(ld64(d + doff) ^ sec64(soff), ld64(d + doff + 8) ^ sec64(soff + 8));
-}
 
 // hashSmall for 9..16 bytes given the two overlapping 8-byte words (xxh3.go:62-66)
 __device__ __forceinline__ uint64_t hash_9to16(uint64_t w_lo, uint64_t w_hi, uint32_t len) {
@@ -121,38 +114,6 @@ __device__ __forceinline__ uint64_t hash_upto16(const uint8_t* d, uint32_t len) 
     return avalanche_small(acc);
 }
 
-#if !HALO_XXH3_FUSED_SHORT
-// xxh3HashCode for len <= 240 (xxh3.go:43-129), one lane
-__device__ uint64_t hash_short(const uint8_t* d, uint32_t len) {
-    if (len <= 16) return hash_upto16(d, len);
-    uint64_t acc = (uint64_t)len * P64_1;
-    if (len <= 128) {  // hashMedium (xxh3.go:94-113)
-        if (len > 32) {
-            if (len > 64) {
-                if (len > 96) {
-                    acc += mix16(d, 48, 96);
-                    acc += mix16(d, len - 64, 112);
-                }
-                acc += mix16(d, 32, 64);
-                acc += mix16(d, len - 48, 80);
-            }
-            acc += mix16(d, 16, 32);
-            acc += mix16(d, len - 32, 48);
-        }
-        acc += mix16(d, 0, 0);
-        acc += mix16(d, len - 16, 16);
-        return avalanche(acc);
-    }
-    // hashLarge (xxh3.go:116-129)
-#pragma unroll 2
-    for (uint32_t off = 0; off < 128; off += 16) acc += mix16(d, off, off);
-    acc = avalanche(acc);
-    for (uint32_t off = 128, top = len & ~15u; off < top; off += 16) acc += mix16(d, off, off - 125);
-    acc += mix16(d, len - 16, 119);
-    return avalanche(acc);
-}
-#endif
-
 // a 64-bit DPP move (both halves with the same control)
 template <int CTRL>
 __device__ __forceinline__ uint64_t dpp64(uint64_t v) {
@@ -160,8 +121,6 @@ __device__ __forceinline__ uint64_t dpp64(uint64_t v) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
     return join64(lo, hi);
 }
-// 64-bit value of lane (lane ^ 1) within each quad (DPP quad_perm 1,0,3,2)
-__device__ __forceinline__ uint64_t swap_pair(uint64_t v) { return dpp64<0xB1>(v); }
 
 // Secret words the long path needs, staged in LDS once per block: the 64-bit word at byte 8k
 // (k = 0..23: stripe secrets, k = 16 + j: scramble), at 121 + 8j (last stripe) and at 11 + 8j
@@ -184,205 +143,16 @@ __device__ __forceinline__ void load_secrets(LongSecrets& s) {  // needs >= 58 t
     else if (t < 58) s.mlast[t - 56] = sec64(119 + 8 * (t - 56));
 }
 
-// accumulateStripe (xxh3.go:181-209) for accumulator j on lane j: `in` = input word j of the stripe
-__device__ __forceinline__ void stripe_acc(uint64_t& acc, uint64_t in, uint64_t secret) {
-    const uint64_t k = in ^ secret;
-    acc += swap_pair(in) + (uint64_t)(uint32_t)k * (k >> 32);
-}
-
-#ifndef HALO_XXH3_X3
-#define HALO_XXH3_X3 1
-#endif
-// Stripes per load batch and threads per block of the long kernel: 4 and one-wave blocks
-// (profiles/r02/ab_xxh3_batch_block.log: 8 / 16 stripes 11 / 30 % slower, one-wave blocks 2 %
-// faster than 256-thread ones).
-#ifndef HALO_XXH3_BATCH
-#define HALO_XXH3_BATCH 4
-#endif
-#ifndef HALO_XXH3_LONG_BLOCK
-#define HALO_XXH3_LONG_BLOCK 64
-#endif
-// hashLong (xxh3.go:132-178) on a group of 8 lanes; lane j = accumulator j. Result in every lane.
-// Stripe words are read as aligned dwords (three when the string is not 4-byte aligned) four
-// stripes at a time, so a lane has up to 12 loads in flight.
-[[maybe_unused]] __device__ uint64_t hash_long8(const uint8_t* d, uint32_t len, uint32_t j, const LongSecrets& sec) {
-    constexpr uint64_t kInit[8] = {P32_3, P64_1, P64_2, P64_3, P64_4, P32_2, P64_5, P32_1};
-    uint64_t acc = kInit[0];
-#pragma unroll
-    for (int q = 1; q < 8; ++q) acc = j == (uint32_t)q ? kInit[q] : acc;
-    const uintptr_t base = reinterpret_cast<uintptr_t>(d);
-    const uint32_t sh = (uint32_t)(base & 3u);  // uniform per group
-    gdw* q0 = (gdw*)(base & ~(uintptr_t)3) + 2 * j;
-    // Input word j of stripe `stripe`: three dwords in one load instruction (global_load_dwordx3)
-    // whatever the alignment. The third is read even when the string is dword-aligned: every
-    // stripe of this loop ends at least one byte before the string does, so that dword still
-    // holds a string byte (never a page the string is not on).
-#if HALO_XXH3_X3
-    typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-    typedef const __attribute__((address_space(1))) u32x3 gdw3;
-    auto word = [&](uint32_t stripe) -> uint64_t {
-        const u32x3 v = *(gdw3*)(q0 + 16 * stripe);
-        return join64(__builtin_amdgcn_alignbyte(v.y, v.x, sh), __builtin_amdgcn_alignbyte(v.z, v.y, sh));
-    };
-#else
-    auto word = [&](uint32_t stripe) -> uint64_t {  // input word j of stripe `stripe`
-        gdw* r = q0 + 16 * stripe;
-        const uint32_t w0 = r[0], w1 = r[1];
-        const uint32_t w2 = sh ? r[2] : 0u;
-        return join64(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh));
-    };
-#endif
-    constexpr uint32_t B = HALO_XXH3_BATCH;  // stripes whose loads are issued together
-    uint32_t stripe = 0, remaining = len;
-    while (remaining > 1024) {
-#pragma unroll 1
-        for (uint32_t st = 0; st < 16; st += B) {
-            uint64_t w[B];
-#pragma unroll
-            for (uint32_t u = 0; u < B; ++u) w[u] = word(stripe + st + u);
-#pragma unroll
-            for (uint32_t u = 0; u < B; ++u) stripe_acc(acc, w[u], sec.w8[st + u + j]);
-        }
-        stripe += 16;
-        remaining -= 1024;
-        acc ^= acc >> 47;  // scramble (xxh3.go:212-218)
-        acc ^= sec.w8[16 + j];
-        acc *= P32_1;
-    }
-    const uint32_t stripes = (remaining - 1) / 64;
-    uint32_t st = 0;
-    for (; st + B <= stripes; st += B) {
-        uint64_t w[B];
-#pragma unroll
-        for (uint32_t u = 0; u < B; ++u) w[u] = word(stripe + st + u);
-#pragma unroll
-        for (uint32_t u = 0; u < B; ++u) stripe_acc(acc, w[u], sec.w8[st + u + j]);
-    }
-    for (; st < stripes; ++st) stripe_acc(acc, word(stripe + st), sec.w8[st + j]);
-    stripe_acc(acc, ld64(d + len - 64 + 8 * j), sec.last[j]);  // last stripe, secret offset 121
-    // merge (xxh3.go:139-145): pairs (2i, 2i+1) with secret 11 + 16i, then sum over the pairs
-    const uint64_t mine = acc ^ sec.merge[j];
-    const uint64_t other = swap_pair(mine);
-    uint64_t m = (j & 1u) ? 0ull : mul_fold64(mine, other);
-    // sum lanes 0, 2, 4, 6 of the group (odd lanes hold 0): butterfly over the 8 lanes
-    m += dpp64<0xB1>(m);   // quad_perm 1,0,3,2
-    m += dpp64<0x4E>(m);   // quad_perm 2,3,0,1
-    m += dpp64<0x141>(m);  // row_half_mirror: lane i <-> 7-i within each 8
-    return avalanche((uint64_t)len * P64_1 + m);
-}
-
 // hashLong on a group of 4 lanes: lane j owns accumulators 2j and 2j+1 and reads input words 2j
 // and 2j+1 of each stripe (bytes [16j, 16j+16): one 16-byte load), so the i ^ 1 exchange of
 // accumulateStripe (xxh3.go:181-209) stays inside the lane — no DPP swap — and a wave-instruction
 // reads 16 strings' 64-byte stripes. The load is unaligned (gfx9 global loads accept any byte
 // address; the 16 bytes are all string bytes, so no other page is touched).
 typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-#ifndef HALO_XXH3_NT  // non-temporal string loads (the bytes are read once, bar run boundaries)
-#define HALO_XXH3_NT 0
-#endif
 __device__ __forceinline__ void ld128u(const uint8_t* p, uint64_t& lo, uint64_t& hi) {
-#if HALO_XXH3_NT
-    const u32x4u v = __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4u*)p);
-#else
     const u32x4u v = *(const __attribute__((address_space(1))) u32x4u*)p;
-#endif
     lo = join64(v.x, v.y);
     hi = join64(v.z, v.w);
-}
-__device__ __forceinline__ void stripe_acc2(uint64_t& a0, uint64_t& a1, uint64_t in0, uint64_t in1, uint64_t s0,
-                                            uint64_t s1) {
-    const uint64_t k0 = in0 ^ s0, k1 = in1 ^ s1;
-    a0 += in1 + (uint64_t)(uint32_t)k0 * (k0 >> 32);
-    a1 += in0 + (uint64_t)(uint32_t)k1 * (k1 >> 32);
-}
-[[maybe_unused]] __device__ uint64_t hash_long4(const uint8_t* d, uint32_t len, uint32_t j, const LongSecrets& sec) {
-    constexpr uint64_t kInit[8] = {P32_3, P64_1, P64_2, P64_3, P64_4, P32_2, P64_5, P32_1};
-    uint64_t a0 = kInit[0], a1 = kInit[1];
-#pragma unroll
-    for (int q = 1; q < 4; ++q) {
-        a0 = j == (uint32_t)q ? kInit[2 * q] : a0;
-        a1 = j == (uint32_t)q ? kInit[2 * q + 1] : a1;
-    }
-    const uint8_t* q0 = d + 16 * j;
-    constexpr uint32_t B = HALO_XXH3_BATCH;  // stripes whose loads are issued together
-    uint32_t stripe = 0, remaining = len;
-    while (remaining > 1024) {
-#pragma unroll 1
-        for (uint32_t st = 0; st < 16; st += B) {
-            uint64_t lo[B], hi[B];
-#pragma unroll
-            for (uint32_t u = 0; u < B; ++u) ld128u(q0 + 64 * (stripe + st + u), lo[u], hi[u]);
-#pragma unroll
-            for (uint32_t u = 0; u < B; ++u)
-                stripe_acc2(a0, a1, lo[u], hi[u], sec.w8[st + u + 2 * j], sec.w8[st + u + 2 * j + 1]);
-        }
-        stripe += 16;
-        remaining -= 1024;
-        a0 ^= a0 >> 47;  // scramble (xxh3.go:212-218)
-        a1 ^= a1 >> 47;
-        a0 ^= sec.w8[16 + 2 * j];
-        a1 ^= sec.w8[17 + 2 * j];
-        a0 *= P32_1;
-        a1 *= P32_1;
-    }
-    const uint32_t stripes = (remaining - 1) / 64;
-    uint32_t st = 0;
-    for (; st + B <= stripes; st += B) {
-        uint64_t lo[B], hi[B];
-#pragma unroll
-        for (uint32_t u = 0; u < B; ++u) ld128u(q0 + 64 * (stripe + st + u), lo[u], hi[u]);
-#pragma unroll
-        for (uint32_t u = 0; u < B; ++u)
-            stripe_acc2(a0, a1, lo[u], hi[u], sec.w8[st + u + 2 * j], sec.w8[st + u + 2 * j + 1]);
-    }
-    for (; st < stripes; ++st) {
-        uint64_t lo, hi;
-        ld128u(q0 + 64 * (stripe + st), lo, hi);
-        stripe_acc2(a0, a1, lo, hi, sec.w8[st + 2 * j], sec.w8[st + 2 * j + 1]);
-    }
-    {  // last stripe, secret offset 121
-        uint64_t lo, hi;
-        ld128u(d + len - 64 + 16 * j, lo, hi);
-        stripe_acc2(a0, a1, lo, hi, sec.last[2 * j], sec.last[2 * j + 1]);
-    }
-    // merge (xxh3.go:139-145): pair (2j, 2j+1) with secret 11 + 16j on lane j, summed over the quad
-    uint64_t m = mul_fold64(a0 ^ sec.merge[2 * j], a1 ^ sec.merge[2 * j + 1]);
-    m += dpp64<0xB1>(m);  // quad_perm 1,0,3,2
-    m += dpp64<0x4E>(m);  // quad_perm 2,3,0,1
-    return avalanche((uint64_t)len * P64_1 + m);
-}
-
-// hashMedium / hashLarge (xxh3.go:94-129, 17..240 bytes) on a group of 8 lanes. Both are sums of
-// independent mix16 terms (wrapping 64-bit adds: any order), so each lane takes one term — its 16
-// data bytes in one unaligned load, always inside the string — and a butterfly sums them:
-// hashMedium's pairs (16k, len-16-16k) on lanes 2k / 2k+1, hashLarge's first eight terms on
-// lanes 0..7, an avalanche, then its middle terms and the last one the same way.
-__device__ __forceinline__ uint64_t mix16u(const uint8_t* p, uint32_t soff) {
-    uint64_t lo, hi;
-    ld128u(p, lo, hi);
-    return mul_fold64(lo ^ sec64(soff), hi ^ sec64(soff + 8));
-}
-__device__ __forceinline__ uint64_t sum8(uint64_t v) {
-    v += dpp64<0xB1>(v);   // quad_perm 1,0,3,2
-    v += dpp64<0x4E>(v);   // quad_perm 2,3,0,1
-    v += dpp64<0x141>(v);  // row_half_mirror: lane i <-> 7-i within each 8
-    return v;
-}
-[[maybe_unused]] __device__ uint64_t hash_mid8(const uint8_t* d, uint32_t len, uint32_t l) {
-    uint64_t v = 0;
-    if (len <= 128) {
-        const uint32_t levels = len > 96 ? 4u : len > 64 ? 3u : len > 32 ? 2u : 1u;
-        const uint32_t k = l >> 1, side = l & 1u;
-        if (k < levels) v = mix16u(d + (side ? len - 16 - 16 * k : 16 * k), 32 * k + 16 * side);
-        return avalanche((uint64_t)len * P64_1 + sum8(v));
-    }
-    v = mix16u(d + 16 * l, 16 * l);
-    const uint64_t acc = avalanche((uint64_t)len * P64_1 + sum8(v));
-    const uint32_t nmid = ((len & ~15u) - 128) / 16;  // 0..7 middle terms, then the last one
-    v = 0;
-    if (l < nmid) v = mix16u(d + 128 + 16 * l, 3 + 16 * l);
-    else if (l == nmid) v = mix16u(d + len - 16, 119);
-    return avalanche(acc + sum8(v));
 }
 
 struct XxhParams {
@@ -394,156 +164,7 @@ struct XxhParams {
     uint32_t win;  // strings per wave of the run kernel (<= kRunWin)
 };
 
-// strings <= 240 B (the long ones are left to xxh3_long_kernel). A wave scans kShortScan strings
-// and compacts the short ones into LDS by class — 129..240 B, then 17..128 B, then <= 16 B — so a
-// round's groups mostly take the same branch. 17..240 B strings are hashed eight at a time on
-// 8-lane groups (hash_mid8: one 16-byte term per lane), <= 16 B ones a lane each (hash_short).
-// Lane-per-string for 17..240 B (up to 23 dependent mix16 terms, every lane gathering 4-byte words
-// of a different string) ran at ~0.5 TB/s.
-#if !HALO_XXH3_FUSED_SHORT
-#ifndef HALO_XXH3_SHORT_SCAN
-#define HALO_XXH3_SHORT_SCAN 256
-#endif
-constexpr uint32_t kShortScan = HALO_XXH3_SHORT_SCAN;  // strings per wave window (a multiple of 64)
-__global__ void __launch_bounds__(256) xxh3_short_kernel(const XxhParams p) {
-    __shared__ uint32_t s_idx[4][kShortScan];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-    const uint32_t g = lane >> 3, l = lane & 7u;
-    for (uint32_t base = wave * kShortScan; base < p.n; base += nwaves * kShortScan) {
-        uint32_t len[kShortScan / 64];
-#pragma unroll
-        for (uint32_t k = 0; k < kShortScan / 64; ++k) {
-            const uint32_t i = base + 64 * k + lane;
-            len[k] = i < p.n ? p.lens[i] : 0xFFFFFFFFu;
-        }
-        uint32_t cnt = 0, n_mid = 0;
-#pragma unroll
-        for (int pass = 0; pass < 3; ++pass) {
-#pragma unroll
-            for (uint32_t k = 0; k < kShortScan / 64; ++k) {
-                const bool take = pass == 0 ? (len[k] > 128 && len[k] <= 240)
-                                : pass == 1 ? (len[k] > 16 && len[k] <= 128) : len[k] <= 16;
-                const uint64_t b = __ballot(take);
-                if (take)
-                    s_idx[w][cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32),
-                                                              __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u))] =
-                        base + 64 * k + lane;
-                cnt += (uint32_t)__popcll(b);
-            }
-            if (pass == 1) n_mid = cnt;
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t r = 0; r < n_mid; r += 8) {
-            const uint32_t e = r + g;
-            if (e < n_mid) {  // uniform per group
-                const uint32_t i = s_idx[w][e];
-                const uint64_t h = hash_mid8(p.bytes + p.offsets[i], p.lens[i], l);
-                if (l == 0) p.out[i] = h;
-            }
-        }
-        for (uint32_t e = n_mid + lane; e < ((cnt - n_mid + 63) & ~63u) + n_mid; e += 64) {
-            if (e < cnt) {
-                const uint32_t i = s_idx[w][e];
-                p.out[i] = hash_short(p.bytes + p.offsets[i], p.lens[i]);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-#endif
-
-// strings > 240 B: each wave scans 64 strings, ranks its long ones by length (longest first) and
-// hashes them sixteen at a time, one per 4-lane group (eight per 8-lane group with
-// HALO_XXH3_LANES=8) — rank order keeps the strings of a round about equally long, so groups do
-// not idle behind the round's longest string
-#ifndef HALO_XXH3_RUNS
-#define HALO_XXH3_RUNS 1  // the run kernel below (0: this round-3 kernel, kept for A/B)
-#endif
-#if !HALO_XXH3_RUNS
-#ifndef HALO_XXH3_LANES
-#define HALO_XXH3_LANES 4  // lanes per long string: 4 (hash_long4) or 8 (hash_long8)
-#endif
-#ifndef HALO_XXH3_LONG_WAVES
-#define HALO_XXH3_LONG_WAVES 0  // amdgpu_waves_per_eu for the long kernel (0: the compiler's choice)
-#endif
-__global__ void __launch_bounds__(HALO_XXH3_LONG_BLOCK)
-#if HALO_XXH3_LONG_WAVES
-__attribute__((amdgpu_waves_per_eu(HALO_XXH3_LONG_WAVES)))
-#endif
-xxh3_long_kernel(const XxhParams p) {
-    constexpr uint32_t LN = HALO_XXH3_LANES, GPW = 64 / LN;  // strings per round
-    __shared__ LongSecrets s_sec;
-    __shared__ uint8_t s_order[HALO_XXH3_LONG_BLOCK / 64][64];  // per wave: lane holding the string of each rank
-    load_secrets(s_sec);
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t w = threadIdx.x >> 6;
-    const uint32_t g = lane / LN, j = lane & (LN - 1);
-    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-    for (uint32_t base = wave * 64; base < p.n; base += nwaves * 64) {
-        const uint32_t i = base + lane;
-        const uint32_t raw = i < p.n ? p.lens[i] : 0u;
-        const uint32_t len = raw > 240 ? raw : 0u;
-        const uint32_t nlong = (uint32_t)__popcll(__ballot(len != 0));
-        if (!HALO_XXH3_FUSED_SHORT && nlong == 0) continue;
-        if (nlong) {
-            // rank = number of lanes with a longer string, ties by lane
-            uint32_t rank = 0;
-#pragma unroll
-            for (int k = 0; k < 64; ++k) {
-                const uint32_t lk = (uint32_t)__builtin_amdgcn_readlane((int)len, k);
-                rank += (lk > len || (lk == len && (uint32_t)k < lane)) ? 1u : 0u;
-            }
-            if (len) s_order[w][rank] = (uint8_t)lane;
-            __builtin_amdgcn_wave_barrier();
-            for (uint32_t r0 = 0; r0 < nlong; r0 += GPW) {
-                const uint32_t rk = r0 + g;
-                if (rk < nlong) {  // uniform per group
-                    const uint32_t owner = s_order[w][rk];
-                    const uint32_t idx = base + owner;
-                    const uint64_t h = LN == 4 ? hash_long4(p.bytes + p.offsets[idx], p.lens[idx], j, s_sec)
-                                               : hash_long8(p.bytes + p.offsets[idx], p.lens[idx], j, s_sec);
-                    if (j == 0) p.out[idx] = h;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-#if HALO_XXH3_FUSED_SHORT
-        // the window's short strings in the same wave: lines they share with the long strings just
-        // hashed are still in the L2, and the window's 64 hashes are written by one wave.
-        // 129..240 B, then 17..128 B on 8-lane groups (hash_mid8; classes kept apart so that a
-        // round's groups take one branch), <= 16 B a lane each.
-        const bool in = i < p.n;
-        const uint64_t b_large = __ballot(in && raw > 128 && raw <= 240);
-        const uint64_t b_med = __ballot(in && raw > 16 && raw <= 128);
-        const uint32_t n_large = (uint32_t)__popcll(b_large), n_mid = n_large + (uint32_t)__popcll(b_med);
-        if (in && raw > 128 && raw <= 240)
-            s_order[w][__builtin_amdgcn_mbcnt_hi((uint32_t)(b_large >> 32),
-                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)b_large, 0u))] = (uint8_t)lane;
-        if (in && raw > 16 && raw <= 128)
-            s_order[w][n_large + __builtin_amdgcn_mbcnt_hi((uint32_t)(b_med >> 32),
-                                                           __builtin_amdgcn_mbcnt_lo((uint32_t)b_med, 0u))] = (uint8_t)lane;
-        __builtin_amdgcn_wave_barrier();
-        for (uint32_t r0 = 0; r0 < n_mid; r0 += 8) {
-            const uint32_t e = r0 + (lane >> 3);
-            if (e < n_mid) {  // uniform per 8-lane group
-                const uint32_t idx = base + s_order[w][e];
-                const uint64_t h = hash_mid8(p.bytes + p.offsets[idx], p.lens[idx], lane & 7u);
-                if ((lane & 7u) == 0) p.out[idx] = h;
-            }
-        }
-        if (in && raw <= 16) p.out[i] = hash_upto16(p.bytes + p.offsets[i], raw);
-        __builtin_amdgcn_wave_barrier();
-#endif
-    }
-}
-#endif  // !HALO_XXH3_RUNS
-
-
-// ---- the run kernel (HALO_XXH3_RUNS, the default) ---------------------------------------------
+// ---- the run kernel ---------------------------------------------------------------------------
 // the per-class kernels fetched 1.29x the algorithmic bytes — strings packed one byte
 // apart share their first and last 128-byte lines with their neighbours, and a neighbour was hashed
 // at another time (a length-ranked round, or the short-string pass), by then evicted from the L2 —
@@ -560,11 +181,8 @@ xxh3_long_kernel(const XxhParams p) {
 // hashMedium / hashLarge (:94-129, two or four per lane), so all groups share one memory round trip
 // per iteration whatever mix of strings they hold. Strings of <= 16 B take hashSmall (:59-91). The
 // window's hashes collect in LDS and leave as whole lines in string order.
-#ifndef HALO_XXH3_WIN
-#define HALO_XXH3_WIN 256
-#endif
-constexpr uint32_t kRunWin = HALO_XXH3_WIN;  // strings per wave (a multiple of 64)
-[[maybe_unused]] constexpr uint32_t kRunPer = kRunWin / 64;
+constexpr uint32_t kRunWin = 256;  // strings per wave (a multiple of 64)
+constexpr uint32_t kRunPer = kRunWin / 64;
 struct RunLds {
     uint64_t off[kRunWin];
     uint64_t hash[kRunWin];
@@ -574,54 +192,26 @@ struct RunLds {
 
 // Stripes per iteration of a long string (16-byte loads per lane in flight): 8 halves the
 // dependent memory round trips a wave makes (a window of 256 KCP-sized strings is ~56 of them at 4)
-#ifndef HALO_XXH3_RUN_B
-#define HALO_XXH3_RUN_B 8
-#endif
-constexpr uint32_t kRunB = HALO_XXH3_RUN_B;
+constexpr uint32_t kRunB = 8;
 static_assert(kRunB == 4 || kRunB == 8 || kRunB == 16, "a batch must not straddle a 16-stripe block");
-[[maybe_unused]] __device__ __forceinline__ uint32_t run_cost(uint32_t len) {
+__device__ __forceinline__ uint32_t run_cost(uint32_t len) {
     return len > 240 ? ((len - 1) / 64 + kRunB) / kRunB : 1u;  // ceil((T + 1) / B), T = loop stripes
 }
 
-[[maybe_unused]] __device__ __forceinline__ uint64_t quad_sum(uint64_t v) {
+__device__ __forceinline__ uint64_t quad_sum(uint64_t v) {
     v += dpp64<0xB1>(v);  // quad_perm 1,0,3,2
     v += dpp64<0x4E>(v);  // quad_perm 2,3,0,1
     return v;
 }
 
-// Branch-free iteration (HALO_XXH3_BF): every lane issues all kRunB loads, an idle slot (past a
-// string's last stripe, a short string, a finished group) reading this zero line instead of
-// branching around the load; the long path selects secrets and drops terms past the last stripe.
-#ifndef HALO_XXH3_BF
-#define HALO_XXH3_BF 1
-#endif
+// Branch-free iteration: every lane issues all kRunB loads, an idle slot (past a string's last
+// stripe, a short string, a finished group) reading this zero line instead of branching around
+// the load; the long path selects secrets and drops terms past the last stripe.
 #ifndef HALO_XXH3_PROBE  // tools only: the run kernel's loads without the hashing (wrong hashes)
 #define HALO_XXH3_PROBE 0
 #endif
-#ifndef HALO_XXH3_MERGED  // one finishing sequence for long merges and 17..240 B strings
-#define HALO_XXH3_MERGED 0   // measured slower: 0.189 / 0.189 ms against 0.188 / 0.186 (profiles/r04/r4i)
-#endif
-// Dword-aligned loads (HALO_XXH3_ALIGNED): the 16 bytes at any address as an aligned 16-byte load
-// plus one dword, merged with v_alignbyte, instead of one byte-unaligned 16-byte load
-#ifndef HALO_XXH3_ALIGNED
-#define HALO_XXH3_ALIGNED 0  // measured slower: 0.214 / 0.214 ms against 0.185 / 0.185 (profiles/r04/r4j)
-#endif
-[[maybe_unused]] __device__ __forceinline__ void ld128a(const uint8_t* p, uint64_t& lo, uint64_t& hi) {
-    typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    const uint32_t sh = (uint32_t)(a & 3u);
-    const uintptr_t q = a & ~(uintptr_t)3;
-    const u32x4a v = *(const __attribute__((address_space(1))) u32x4a*)q;
-    // the fifth dword holds bytes 16 - sh .. 15 of the span when sh != 0; else any dword inside it
-    const uint32_t w4 = *(const __attribute__((address_space(1))) uint32_t*)(q + (sh ? 16 : 12));
-    lo = join64(__builtin_amdgcn_alignbyte(v.y, v.x, sh), __builtin_amdgcn_alignbyte(v.z, v.y, sh));
-    hi = join64(__builtin_amdgcn_alignbyte(v.w, v.z, sh), __builtin_amdgcn_alignbyte(w4, v.w, sh));
-}
-#if HALO_XXH3_BF
 __device__ const uint8_t g_xxh3_pad[64] = {};
-#endif
 
-#if HALO_XXH3_RUNS
 __global__ void __launch_bounds__(64) xxh3_run_kernel(const XxhParams p) {
     __shared__ LongSecrets sec;
     __shared__ RunLds s;
@@ -702,14 +292,7 @@ __global__ void __launch_bounds__(64) xxh3_run_kernel(const XxhParams p) {
                 v = u < 2 || t <= nmid;
                 a = u < 2 ? d + 16 * t : t < nmid ? d + 128 + 16 * t : d + len - 16;
             }
-#if HALO_XXH3_BF && HALO_XXH3_ALIGNED
-            ld128a(v ? a : g_xxh3_pad, lo[u], hi[u]);  // no branch: idle slots read 16 zero bytes
-#elif HALO_XXH3_BF
             ld128u(v ? a : g_xxh3_pad, lo[u], hi[u]);
-#else
-            lo[u] = hi[u] = 0;
-            if (v) ld128u(a, lo[u], hi[u]);
-#endif
         }
         uint64_t h = 0;
         bool have = false;
@@ -731,62 +314,11 @@ __global__ void __launch_bounds__(64) xxh3_run_kernel(const XxhParams p) {
             h = lo[0] ^ hi[0] ^ lo[1] ^ hi[1] ^ lo[2] ^ hi[2] ^ lo[3] ^ hi[3];
             have = true;
         }
-#elif HALO_XXH3_MERGED
-        bool fin = false;
-        if (lng) {
-#pragma unroll
-            for (uint32_t u = 0; u < kRunB; ++u) {
-                const uint32_t x = st + u;
-                const uint64_t s0 = x < T ? sec.w8[(x & 15u) + 2 * j] : sec.last[2 * j];
-                const uint64_t s1 = x < T ? sec.w8[(x & 15u) + 2 * j + 1] : sec.last[2 * j + 1];
-                const uint64_t k0 = lo[u] ^ s0, k1 = hi[u] ^ s1;
-                const uint64_t t0 = hi[u] + (uint64_t)(uint32_t)k0 * (k0 >> 32);
-                const uint64_t t1 = lo[u] + (uint64_t)(uint32_t)k1 * (k1 >> 32);
-                a0 += x <= T ? t0 : 0ull;
-                a1 += x <= T ? t1 : 0ull;
-            }
-            st += kRunB;
-            if ((st & 15u) == 0 && (st >> 4) <= nb) {  // a full block ended: scramble (xxh3.go:212-218)
-                a0 ^= a0 >> 47;
-                a1 ^= a1 >> 47;
-                a0 ^= sec.w8[16 + 2 * j];
-                a1 ^= sec.w8[17 + 2 * j];
-                a0 *= P32_1;
-                a1 *= P32_1;
-            }
-            fin = st > T;
-        }
-        // One finishing sequence for a long string's merge (xxh3.go:139-145: pair (2j, 2j+1) with
-        // secret 11 + 16j) and a 17..240 B string's first terms (hashMedium's pair j, hashLarge's
-        // terms 2j and 2j+1: the same secret words 32j .. 32j+24), run by the whole wave once
-        // instead of once per branch; then hashLarge's middle terms and one final avalanche.
-        const bool lend = lng && fin;
-        if (__builtin_amdgcn_ballot_w64(lend || mid)) {
-            const uint64_t A = lend ? a0 ^ sec.merge[2 * j] : lo[0] ^ sec.w8[4 * j];
-            const uint64_t Bq = lend ? a1 ^ sec.merge[2 * j + 1] : hi[0] ^ sec.w8[4 * j + 1];
-            uint64_t t = mul_fold64(A, Bq);
-            if (mid) t += mul_fold64(lo[1] ^ sec.w8[4 * j + 2], hi[1] ^ sec.w8[4 * j + 3]);
-            if (mid && !large && j >= lv) t = 0;
-            uint64_t x = (uint64_t)len * P64_1 + quad_sum(t);
-            if (mid && large) {  // hashLarge: avalanche, then terms 2j, 2j+1 of the middle + last
-                uint64_t t23 = 0;
-#pragma unroll
-                for (uint32_t u = 2; u < 4; ++u) {
-                    const uint32_t q = 2 * j + (u & 1u);
-                    if (q < nmid) t23 += mul_fold64(lo[u] ^ sec.mid3[2 * q], hi[u] ^ sec.mid3[2 * q + 1]);
-                    else if (q == nmid) t23 += mul_fold64(lo[u] ^ sec.mlast[0], hi[u] ^ sec.mlast[1]);
-                }
-                x = avalanche(x) + quad_sum(t23);
-            }
-            h = avalanche(x);
-            have = lend || mid;
-        }
 #else
         if (lng) {
 #pragma unroll
             for (uint32_t u = 0; u < kRunB; ++u) {
                 const uint32_t x = st + u;
-#if HALO_XXH3_BF
                 // select the secret and drop the term past the last stripe instead of branching
                 const uint64_t s0 = x < T ? sec.w8[(x & 15u) + 2 * j] : sec.last[2 * j];
                 const uint64_t s1 = x < T ? sec.w8[(x & 15u) + 2 * j + 1] : sec.last[2 * j + 1];
@@ -795,10 +327,6 @@ __global__ void __launch_bounds__(64) xxh3_run_kernel(const XxhParams p) {
                 const uint64_t t1 = lo[u] + (uint64_t)(uint32_t)k1 * (k1 >> 32);
                 a0 += x <= T ? t0 : 0ull;
                 a1 += x <= T ? t1 : 0ull;
-#else
-                if (x < T) stripe_acc2(a0, a1, lo[u], hi[u], sec.w8[(x & 15u) + 2 * j], sec.w8[(x & 15u) + 2 * j + 1]);
-                else if (x == T) stripe_acc2(a0, a1, lo[u], hi[u], sec.last[2 * j], sec.last[2 * j + 1]);
-#endif
             }
             st += kRunB;
             if ((st & 15u) == 0 && (st >> 4) <= nb) {  // a full block ended: scramble (xxh3.go:212-218)
@@ -854,11 +382,27 @@ __global__ void __launch_bounds__(64) xxh3_run_kernel(const XxhParams p) {
         if (r < cnt) p.out[base + r] = s.hash[r];
     }
 }
-#endif  // HALO_XXH3_RUNS
 
 // Tried and removed (round 4; in git history up to commit 68eed30): the run kernel
 // on 8 groups of 8 lanes (128 contiguous bytes per string per load instruction) and a software-
 // pipelined run kernel (step k + 1's loads before step k's arithmetic). Both bit-exact, both slower.
+//
+// Tried and removed (in git history up to commit 9ac2a89), each bit-exact:
+//  - the round-3 pair of kernels the run kernel replaced: a short-string kernel (a wave compacted 256
+//    strings by class; 17..240 B on 8-lane groups, one 16-byte mix16 term per lane; lane-per-string
+//    for those lengths, every lane gathering 4-byte words of a different string, ran at ~0.5 TB/s) and
+//    a long-string kernel (a wave ranked its 64 strings by length and hashed the long ones one per
+//    4- or 8-lane group, the short ones optionally in the same wave). Its loads went four stripes at a
+//    time from one-wave blocks: 8 / 16 stripes were 11 / 30 % slower, 256-thread blocks 2 % slower
+//    (profiles/r02/ab_xxh3_batch_block.log). Non-temporal string loads and dwordx3 loads went with it.
+//  - a loop that branched around idle load slots instead of reading the zero line;
+//  - one finishing sequence shared by long merges and 17..240 B strings: 0.189 / 0.189 ms against
+//    0.188 / 0.186 (profiles/r04/r4i);
+//  - dword-aligned loads (an aligned 16-byte load plus one dword, merged with v_alignbyte) instead of
+//    one byte-unaligned 16-byte load: 0.214 / 0.214 ms against 0.185 / 0.185 (profiles/r04/r4j);
+//  - windows sized so that all waves are resident at once (5120 waves = 5 per SIMD at the kernel's
+//    95 VGPRs; 1M strings -> 208-string windows, 5042 waves): 0.199 / 0.200 ms against 0.186 / 0.186
+//    for 256-string windows (4096 waves; profiles/r04/r4h/ab_xxh3_bf.log).
 
 
 // ---- NAT flow keys from parsed records ------------------------------------------------------
@@ -913,7 +457,7 @@ uint32_t blocks_for(uint64_t threads) {
 extern "C" __attribute__((visibility("default"))) int halo_bench_xxh3_probe_launch(
     const uint8_t* d_bytes, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t n, uint64_t* d_hash,
     void* stream) {
-    static_assert(HALO_XXH3_PROBE && HALO_XXH3_RUNS, "the probe entry is the run kernel built as a probe");
+    static_assert(HALO_XXH3_PROBE, "the probe entry is the run kernel built as a probe");
     if (n == 0 || !d_bytes || !d_offsets || !d_lens || !d_hash) return HALO_E_INVAL;
     halo::XxhParams p{d_bytes, d_offsets, d_lens, n, d_hash};
     p.win = halo::kRunWin;
@@ -932,32 +476,10 @@ extern "C" HALO_API int halo_xxh3_64_batch_device(const uint8_t* d_bytes, const 
     if (rc) return rc;
     halo::XxhParams p{d_bytes, d_offsets, d_lens, n, d_hash};
     const hipStream_t s = static_cast<hipStream_t>(stream);
-#if !HALO_XXH3_FUSED_SHORT
-    hipLaunchKernelGGL(halo::xxh3_short_kernel, dim3(halo::blocks_for((n + halo::kShortScan / 64 - 1) /
-                                                                       (halo::kShortScan / 64))),
-                       dim3(256), 0, s, p);
-#endif
-#if HALO_XXH3_RUNS
-    // Window per wave: kRunWin strings, or (HALO_XXH3_WAVES_TARGET, a knob) as many waves as fit the
-    // chip at once, e.g. 5120 = 5 per SIMD at the kernel's 95 VGPRs: 1M strings -> 208-string
-    // windows, 5042 waves all resident. Measured slower: 0.199 / 0.200 ms against 0.186 / 0.186 for
-    // 256-string windows (4096 waves; profiles/r04/r4h/ab_xxh3_bf.log)
-#ifndef HALO_XXH3_WAVES_TARGET
-#define HALO_XXH3_WAVES_TARGET 0
-#endif
-    uint32_t win = halo::kRunWin;
-    if (HALO_XXH3_WAVES_TARGET) {
-        win = (uint32_t)(((uint64_t)n + HALO_XXH3_WAVES_TARGET - 1) / HALO_XXH3_WAVES_TARGET);
-        win = (win + 15u) & ~15u;
-        win = win < 64u ? 64u : win > halo::kRunWin ? halo::kRunWin : win;
-    }
+    // one one-wave block per window of kRunWin strings: no grid-stride loop, no cap on the grid
+    const uint32_t win = halo::kRunWin;
     p.win = win;
     hipLaunchKernelGGL(halo::xxh3_run_kernel, dim3((n + win - 1) / win), dim3(64), 0, s, p);
-#else
-    constexpr uint32_t wpb = HALO_XXH3_LONG_BLOCK / 64;
-    const uint32_t long_blocks = (uint32_t)(((uint64_t)halo::blocks_for(n) * 4 + wpb - 1) / wpb);
-    hipLaunchKernelGGL(halo::xxh3_long_kernel, dim3(long_blocks), dim3(HALO_XXH3_LONG_BLOCK), 0, s, p);
-#endif
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }
 

@@ -100,14 +100,8 @@ int hist_keys_debug(int device, int op, uint32_t arg);
 // data + 4 * off_dw[i], the host's ReadPacket walk wrote off_dw / lens into pinned memory; 64-frame
 // windows dealt round-robin over the groups) and write their records to `out`; each group then
 // publishes its done_seq slot. The host never launches per poll.
-#ifndef HALO_SVC_GROUPS
-#define HALO_SVC_GROUPS 8   // workgroups of the resident consumer (each on its own CU)
-#endif
-#ifndef HALO_SVC_WAVES
-#define HALO_SVC_WAVES 8    // waves per workgroup (64 frames each per pass)
-#endif
-constexpr uint32_t kSvcGroups = HALO_SVC_GROUPS;
-constexpr uint32_t kSvcWaves = HALO_SVC_WAVES;
+constexpr uint32_t kSvcGroups = 8;  // workgroups of the resident consumer (each on its own CU)
+constexpr uint32_t kSvcWaves = 8;   // waves per workgroup (64 frames each per pass)
 struct alignas(64) RingServiceCtl {
     // The request: one 64-byte line. The host writes the fields, then `check` (svc_check of the
     // fields), then req_seq with release. Each workgroup reads the whole line with one 16-lane load

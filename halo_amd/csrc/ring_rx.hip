@@ -378,10 +378,7 @@ __device__ __forceinline__ void guess_tile(const Scan& s, uint32_t t, TileTab& t
     }
 }
 
-#ifndef HALO_RING_GUESS_WAVES
-#define HALO_RING_GUESS_WAVES 4  // waves per tile in A
-#endif
-constexpr uint32_t kGuessWaves = HALO_RING_GUESS_WAVES;
+constexpr uint32_t kGuessWaves = 4;  // waves per tile in A
 
 __global__ void __launch_bounds__(kGuessWaves * 64) ring_guess_kernel(const Scan s) {
     __shared__ TileTab tb;
@@ -394,10 +391,8 @@ __global__ void __launch_bounds__(kGuessWaves * 64) ring_guess_kernel(const Scan
     guess_tile<kGuessWaves>(s, blockIdx.x, tb, s_mx, v);
 }
 
-#ifndef HALO_RING_LINK_THREADS
-#define HALO_RING_LINK_THREADS 512  // 1024: 8.7 us, 256: 10.6, 512: 8.0 for 1M 64 B records (profiles/r05/r5zt)
-#endif
-constexpr uint32_t kLinkThreads = HALO_RING_LINK_THREADS, kLinkWaves = kLinkThreads / 64, kLinkPer = 16;  // 512: a chunk spans 128 MB
+// tried: 1024 threads 8.7 us, 256: 10.6, 512: 8.0 for 1M 64 B records (profiles/r05/r5zt; in git history up to 9ac2a89)
+constexpr uint32_t kLinkThreads = 512, kLinkWaves = kLinkThreads / 64, kLinkPer = 16;  // 512: a chunk spans 128 MB
 constexpr uint32_t kLinkChunk = kLinkThreads * kLinkPer;
 
 // B's second walk of tile J from its real entry `jin` (the guess was wrong): its records to the

@@ -44,46 +44,29 @@
 namespace halo {
 namespace {
 
-// NT: a non-temporal store. The byte-stream kernel's records take it (HALO_RX_STREAM_NT_STORES):
-// IMIX 1.272 -> 1.244 / 1.240 ms on one box (profiles/r06/r6c/ab_nt.log); the lane kernel's do
-// not (1M x 64 B 21.5 -> 22.2 us in the same A/B; §15.4).
-#ifndef HALO_RX_STREAM_NT_STORES
-#define HALO_RX_STREAM_NT_STORES 1
-#endif
-#ifndef HALO_RX_NT_STORES  // every other record store (measurement knob)
-#define HALO_RX_NT_STORES 0
-#endif
+// NT: a non-temporal store. The byte-stream kernel's records take it: IMIX 1.272 -> 1.244 /
+// 1.240 ms on one box (profiles/r06/r6c/ab_nt.log); tried: the lane kernel's too, 1M x 64 B
+// 21.5 -> 22.2 us in the same A/B (§15.4), and every other record store (a measurement knob).
 // WT: a write-through store at agent scope (global_store_dwordx4 ... sc1): the line goes through
 // the XCD's L2 to memory at once, so the release at the end of the launch finds no dirty record
 // lines to write back before the next dependent launch may start. Only for stores
 // that write whole 128-byte lines from one wave instruction (64 lanes x 16 B), or every partial
-// line would go to memory on its own. Five interleaved rounds each, kernel time, parent against
-// the knob (profiles/r07/):
-//   HALO_RX_LANE_WT_STORES (the two batch lane kernels; never the ring service kernel, whose
-//     hand-off to the host is its own protocol): on. 1M x 64 B 22.28-22.70 -> 21.58-22.01 us,
+// line would go to memory on its own. Five interleaved rounds each, kernel time, plain (or, for the
+// stream kernel, non-temporal) stores against write-through ones (profiles/r07/; in git history up
+// to 9ac2a89):
+//   the two batch lane kernels (never the ring service kernel, whose hand-off to the host is its
+//     own protocol): write-through. 1M x 64 B 22.28-22.70 -> 21.58-22.01 us,
 //     4M 75.9-77.8 -> 75.1-75.9 us, 16M 281.9-285.1 -> 279.4-280.5 us; HBM writes per 1M launch
-//     33,554,432 B before and after (no partial lines). HALO_RX_LANE_LDS_PAD re-swept with it:
+//     33,554,432 B before and after (no partial lines). kLaneLdsPad re-swept with it:
 //     4096 gains 1 % at 1M and loses 1.3 % at 16M, 5120 equals 4608; 4608 stays.
-//   HALO_RX_GROUP_WT_STORES (32 B records of the group kernels and the mix kernel's group passes):
-//     off. 1500 B 276.5-295.0 -> 275.3-293.5 us (overlap); jumbo 5760-5777 -> 5736-5759 us, 0.3 %,
+//   the 32 B records of the group kernels and the mix kernel's group passes: plain. Tried:
+//     1500 B 276.5-295.0 -> 275.3-293.5 us (overlap); jumbo 5760-5777 -> 5736-5759 us, 0.3 %,
 //     the ranges 1.3 us apart: too small to call.
-//   HALO_RX_STREAM_WT_STORES (the byte-stream kernel, instead of its non-temporal default): off.
-//     570 B 115.7-119.7 -> 120.9-125.7 us, IMIX 1178-1241 -> 1194-1263 us: slower.
-#ifndef HALO_RX_LANE_WT_STORES
-#define HALO_RX_LANE_WT_STORES 1
-#endif
-#ifndef HALO_RX_GROUP_WT_STORES
-#define HALO_RX_GROUP_WT_STORES 0
-#endif
-#ifndef HALO_RX_STREAM_WT_STORES
-#define HALO_RX_STREAM_WT_STORES 0
-#endif
+//   the byte-stream kernel: non-temporal. Tried: 570 B 115.7-119.7 -> 120.9-125.7 us,
+//     IMIX 1178-1241 -> 1194-1263 us: slower.
 enum : int { kStorePlain = 0, kStoreNt = 1, kStoreWt = 2 };
-constexpr int kStoreDefault = HALO_RX_NT_STORES ? kStoreNt : kStorePlain;
-constexpr int kStoreLane = HALO_RX_LANE_WT_STORES ? kStoreWt : kStoreDefault;
-constexpr int kStoreGroup = HALO_RX_GROUP_WT_STORES ? kStoreWt : kStoreDefault;
-constexpr int kStoreStream = HALO_RX_STREAM_WT_STORES ? kStoreWt : HALO_RX_STREAM_NT_STORES ? kStoreNt : kStorePlain;
-template <int ST = kStoreDefault>
+constexpr int kStoreLane = kStoreWt, kStoreGroup = kStorePlain, kStoreStream = kStoreNt;
+template <int ST = kStorePlain>
 __device__ __forceinline__ void store16(uint4* dst, uint4 v) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     if constexpr (ST == kStoreWt) {
@@ -125,6 +108,8 @@ __device__ __forceinline__ void acc_segment(const uint32_t (&w)[4], uint32_t d0,
 // a u32 with one v_dot2_u32_u16 instead of a 64-bit add. A halves sum keeps the value mod 0xFFFF
 // (2^16 == 1) and is zero exactly when the masked bytes are, which is all fold16 looks at; it stays
 // below 2^32 for any frame (<= 2254 dwords x 2 x 0xFFFF). e8 = 8 * seg_end.
+// (Still a macro: deleting frame_finish's unreachable acc_segment branch reorders scalar moves in
+// the LoChan lane kernels, and the knob retirement changed no kernel. DESIGN.md §24.)
 #ifndef HALO_RX_LANE_DOT2
 #define HALO_RX_LANE_DOT2 1
 #endif
@@ -349,23 +334,17 @@ __device__ __forceinline__ Hist hist_open(const RxParams& p, uint32_t* s_hist) {
 
 // 16-byte chunks per lane issued before the header is parsed (a lane-per-frame lane needs its
 // first 64 bytes). Eight for groups would let a 570 B frame finish in one round trip, but costs
-// ~55 VGPRs (occupancy 5 -> 3) and lost more than it gained; kept as a knob.
-#ifndef HALO_RX_R0_G8
-#define HALO_RX_R0_G8 4  // measurement knob: round-0 chunk rows of the 8-lane kernel
-#endif
-template <int G>
-constexpr int kRound0 = G == 8 ? HALO_RX_R0_G8 : 4;
-// One frame's state between "fetch" (addresses + round-0 loads issued) and "finish".
+// ~55 VGPRs (occupancy 5 -> 3) and lost more than it gained (tried for the 8-lane kernel; in git
+// history up to 9ac2a89).
+constexpr int kRound0 = 4;
 // Later-round loads of the widest groups (jumbo frames) are non-temporal: 9000 B frames 6.08-6.10
 // -> 5.76 ms; for 1500 B on 8 lanes the same hint costs 12 % (290-296 -> 332 us), IMIX 2 %
-// (profiles/r03/r3y/ab_nt.log: HALO_RX_LATER_NT_G 16 / off / 8, two rounds on one box).
-#ifndef HALO_RX_LATER_NT_G
-#define HALO_RX_LATER_NT_G 16
-#endif
-#ifndef HALO_RX_GROUP_XCD
-#define HALO_RX_GROUP_XCD 8  // runs of this many blocks per XCD in the 4- and 8-lane kernels (0/1: off)
-#endif
-template <int G, int R0 = kRound0<G>>
+// (profiles/r03/r3y/ab_nt.log: tried from 16 lanes / off / from 8 lanes, two rounds on one box; in
+// git history up to 9ac2a89).
+constexpr int kLaterNtG = 16;
+constexpr uint32_t kGroupXcd = 8;  // runs of this many blocks per XCD in the 4- and 8-lane kernels
+// One frame's state between "fetch" (addresses + round-0 loads issued) and "finish".
+template <int G, int R0 = kRound0>
 struct FrameState {
     static constexpr int kR0 = R0;
     const uint8_t* frame;
@@ -476,10 +455,8 @@ __device__ __forceinline__ void frame_store(const RxParams& p, uint64_t i, bool 
 // traffic). Every lane of a group calls it with the same i / present (other groups may be doing
 // the same for other frames); `present` false means "no frame": nothing is read or written,
 // but the group still executes the collective steps.
-#ifndef HALO_RX_LATER_CHUNKS
-#define HALO_RX_LATER_CHUNKS 8
-#endif
-template <int G, int FUSE = 0, int U = HALO_RX_LATER_CHUNKS, int R0 = kRound0<G>, bool L3 = false>  // U: 16-byte chunks in flight per lane per later round
+constexpr int kLaterChunks = 8;
+template <int G, int FUSE = 0, int U = kLaterChunks, int R0 = kRound0, bool L3 = false>  // U: 16-byte chunks in flight per lane per later round
 __device__ __forceinline__ void frame_finish(const RxParams& p, uint64_t i, bool present, uint32_t gl,
                                              uint32_t grp_base, FrameState<G, R0>& st, Hist& hist,
                                              uint4* stage = nullptr) {
@@ -535,7 +512,7 @@ __device__ __forceinline__ void frame_finish(const RxParams& p, uint64_t i, bool
             uint32_t x[U][4];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if constexpr (G >= HALO_RX_LATER_NT_G) load4_nt(st.frame, r0 + (u * G + gl) * 4, seg_dw, x[u]);
+                if constexpr (G >= kLaterNtG) load4_nt(st.frame, r0 + (u * G + gl) * 4, seg_dw, x[u]);
                 else load4(st.frame, r0 + (u * G + gl) * 4, seg_dw, x[u]);
             }
 #pragma unroll
@@ -570,9 +547,6 @@ __device__ __forceinline__ void process_frame(const RxParams& p, uint64_t i, boo
 // ~10 us (r4e). Every block of a kernel that counts calls this once, with the whole block.
 // The tree is the one of the launch's HSA queue (halo_common.h): the words assume one launch at a
 // time per tree, and the dispatch packet's barrier bit is what guarantees it.
-#ifndef HALO_HIST_HDR
-#define HALO_HIST_HDR 0  // measurement knob: 1 = every block re-reads its dispatch packet's barrier bit
-#endif
 // key0: the word at the queue's first probe slot as block thread 0 read it when the block started
 // (Hist::key). A key never changes once set, so a stale copy can only read 0, and then the CAS
 // (performed at memory) returns the real key.
@@ -584,11 +558,6 @@ __device__ __forceinline__ void process_frame(const RxParams& p, uint64_t i, boo
 // before round 6).
 static_assert(kHistTrees == 64, "one probe slot per lane of a wave");
 __device__ __forceinline__ unsigned long long* launch_tree(uint32_t* set_u32, unsigned long long key0) {
-#if HALO_HIST_HDR
-    // 100 us per 1M-frame launch: the packet lives in host memory (bench_hist, profiles/r05)
-    const uint16_t hdr = *static_cast<const uint16_t*>((const void*)__builtin_amdgcn_dispatch_ptr());
-    if (!((hdr >> 8) & 1u)) return nullptr;  // HSA_PACKET_HEADER_BARRIER
-#endif
     unsigned long long* set = reinterpret_cast<unsigned long long*>(set_u32);
     const unsigned long long q = launch_queue();
     const uint32_t k0 = tree_slot0(q), lane = threadIdx.x & 63u;
@@ -638,15 +607,15 @@ __device__ __forceinline__ void flush_hist(const RxParams& p, Hist& hist) {
     // us (their completers all finish at the end and queue on one counter, ~10 ns an add). Runs of
     // consecutive blocks complete through the launch instead. DESIGN.md §14.5.
     constexpr unsigned long long kOne = 1ull << 40, kCount = kOne - 1;
-#ifndef HALO_HIST_RUNS
-#define HALO_HIST_RUNS 16  // 0: off. 1M x 64 B: +1.8-2.0 us against +2.1-2.4 for the two-level tree;
-#endif                     // runs of 8: +5.6, of 32: +1.8-2.0 (profiles/r05/r5zz2)
-    if (HALO_HIST_RUNS && g <= kHistSlots * (uint32_t)(HALO_HIST_RUNS ? HALO_HIST_RUNS : 1)) {  // uniform
+    // Tried (profiles/r05/r5zz2; in git history up to 9ac2a89), 1M x 64 B: runs of 16 +1.8-2.0 us
+    // against +2.1-2.4 for the two-level tree alone; runs of 8: +5.6, of 32: +1.8-2.0
+    constexpr uint32_t kHistRuns = 16;
+    if (g <= kHistSlots * kHistRuns) {  // uniform
         // Grids up to 16384 blocks: slot = a run of 16 consecutive blocks. Workgroups are dispatched
         // in order, so the runs complete one after another through the launch instead of all at its
         // end, and each completer adds straight into the caller's counters (one level: the adds
         // arrive spread out, not queued on one counter at the tail).
-        constexpr uint32_t R = HALO_HIST_RUNS ? HALO_HIST_RUNS : 1;
+        constexpr uint32_t R = kHistRuns;
         const uint32_t r = blockIdx.x / R;
         unsigned long long* w = tree + r * kHistStride + t;
         const unsigned long long add = kOne | hist.s[t];
@@ -669,7 +638,7 @@ __device__ __forceinline__ void flush_hist(const RxParams& p, Hist& hist) {
 }
 
 // Uniform batches: G lanes per frame for every frame (G in {1,4,8,16}); 64/G frames per wave.
-template <int G, int LAYOUT, int FUSE, int R0 = kRound0<G>, int U = HALO_RX_LATER_CHUNKS>
+template <int G, int LAYOUT, int FUSE, int R0 = kRound0, int U = kLaterChunks>
 __device__ __forceinline__ void group_kernel_body(const RxParams& p) {
     constexpr uint32_t FPW = 64 / G;  // frames per wave
     __shared__ uint32_t s_hist[HALO_RX_STATUS_COUNT];
@@ -688,8 +657,8 @@ __device__ __forceinline__ void group_kernel_body(const RxParams& p) {
     // contiguous range per XCD read 1.011x but ran 4 % slower). Not for 16 lanes per frame: jumbo
     // frames share a line in 9000 B and ran 0.5 % slower with it.
     uint32_t lblock = blockIdx.x;
-    if constexpr (G <= 8 && HALO_RX_GROUP_XCD > 1) {
-        constexpr uint32_t R = HALO_RX_GROUP_XCD;
+    if constexpr (G <= 8) {
+        constexpr uint32_t R = kGroupXcd;
         const uint32_t b = blockIdx.x, grp = b / (8 * R);
         if ((grp + 1) * 8 * R <= gridDim.x) lblock = grp * 8 * R + (b & 7u) * R + (b >> 3) % R;
     }
@@ -704,7 +673,7 @@ __device__ __forceinline__ void group_kernel_body(const RxParams& p) {
 
 // Lane per frame. The build lands at 76 VGPRs = 6 waves per SIMD; forcing 7 (72 VGPRs) or 8
 // (64, with scratch spills) was not faster (profiles/r01/ab_r2o_lane_waves.log: 22.2 / 27.8 µs vs
-// 21.9 µs on config 2), so the knob HALO_RX_LANE_WAVES stays off. A wave's 64 records are
+// 21.9 µs on config 2; in git history up to 9ac2a89), so no waves-per-EU attribute. A wave's 64 records are
 // consecutive: they are staged in LDS and written with fully coalesced 16-byte stores (a lane
 // writing its own 32 B record at a 32 B stride stored the same bytes 25 % slower:
 // profiles/r01/probe_store_patterns.log).
@@ -713,21 +682,16 @@ __device__ __forceinline__ void group_kernel_body(const RxParams& p) {
 // ST: the store policy of the 64 records (store16). The default is what the ring service kernel
 // takes; the two batch kernels pass kStoreLane.
 //
-// HALO_RX_LANE_FAST: a window whose 64 frames are all plain takes straight-line code (DESIGN.md
+// The fast path: a window whose 64 frames are all plain takes straight-line code (DESIGN.md
 // §15.12). Plain: an Ethernet frame of 61..64 bytes (so each of the four round-0 chunks is one
 // 16-byte load and nothing of the frame lies beyond them), IPv4 with header byte 0x45, not a
 // fragment, UDP, and 28 <= totalLen <= L - 14 (the UDP length check of udp.go:22 included). Whether
 // the lengths qualify is one ballot before the loads, which then carry no bounds test; the header
 // tests are a second ballot once they land. Any other window, a partial last one included, takes
-// frame_finish as before. LoChan packets (LAYOUT 3) always do. 0: the code of the general path alone.
-#ifndef HALO_RX_LANE_FAST
-#define HALO_RX_LANE_FAST 1
-#endif
-#ifndef HALO_RX_LANE_FAST_MAX_WAVES
-#define HALO_RX_LANE_FAST_MAX_WAVES 65536u  // 4M frames: the largest launch measured to gain
-#endif
+// frame_finish as before. LoChan packets (LAYOUT 3) always do.
+constexpr uint32_t kLaneFastMaxWaves = 65536u;  // 4M frames: the largest launch measured to gain
 template <int LAYOUT>
-constexpr bool kLaneFast = HALO_RX_LANE_FAST && !kL3<LAYOUT>;
+constexpr bool kLaneFast = !kL3<LAYOUT>;
 
 // bswap16 of a dword's low half with one v_perm_b32 (selector bytes >= 0x0C give 0x00)
 __device__ __forceinline__ uint32_t lane_total_len(const FrameState<1>& st) {
@@ -877,16 +841,24 @@ __device__ __forceinline__ bool lane_window_fast(const RxParams& p, uint32_t bas
     return true;
 }
 
-template <int LAYOUT, int FUSE, int ST = kStoreDefault>
+// The window on the general path, after frame_loads.
+template <int LAYOUT, int FUSE, int ST>
 __device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t base, uint32_t lane, FrameState<1>& st,
-                                                   uint4* s_rec_w, Hist& hist);
-template <int LAYOUT, int FUSE, int ST = kStoreDefault>
+                                                   uint4* s_rec_w, Hist& hist) {
+    const bool compact = (p.flags & HALO_RX_RECORD_COMPACT) != 0;
+    const uint32_t i = base + lane;
+    frame_finish<1, FUSE, kLaterChunks, kRound0, kL3<LAYOUT>>(p, i, i < p.n, 0, lane, st, hist,
+                                                              &s_rec_w[compact ? lane : 2 * lane]);
+    lane_window_store<ST>(p, base, lane, s_rec_w);
+}
+
+template <int LAYOUT, int FUSE, int ST = kStorePlain>
 __device__ __forceinline__ void lane_window(const RxParams& p, uint32_t base, uint32_t lane, uint4* s_rec_w,
                                            Hist& hist, bool try_fast = true) {
     const uint32_t i = base + lane;
     FrameState<1> st;
     frame_meta<LAYOUT>(p, i, i < p.n, st);
-    if (kLaneFast<LAYOUT> && try_fast) {  // (try_fast is a constant when the knob is off)
+    if (kLaneFast<LAYOUT> && try_fast) {
         // The outcome passes through an empty asm so that the compiler cannot thread the fast
         // attempt's two exits into the general path's entry: as one if / else the blocks are laid out
         // general first, the attempt's loads stay live across all of it, and the kernel needs 87
@@ -899,46 +871,21 @@ __device__ __forceinline__ void lane_window(const RxParams& p, uint32_t base, ui
     lane_window_finish<LAYOUT, FUSE, ST>(p, base, lane, st, s_rec_w, hist);
 }
 
-#ifndef HALO_RX_LANE_WAVES
-#define HALO_RX_LANE_WAVES 0
-#endif
-// Prefetching the next group's address/length in waves that loop: no gain at 1M (22.0 vs 22.1
-// us) and 3 % slower at 16M; with capped grids 2-11 % slower (profiles/r02/ab_lane_prefetch.log).
-#ifndef HALO_RX_LANE_PREFETCH
-#define HALO_RX_LANE_PREFETCH 0
-#endif
-// Threads per block of the lane kernel (64, 128 or 256) and 16-byte chunks per lane in its later
-// load rounds (frames > 64 B only). One-wave blocks with 4.5 KB of LDS padding (22 blocks =
+// Threads per block of the lane kernel and 16-byte chunks per lane in its later load rounds
+// (frames > 64 B only; kLaterChunks). One-wave blocks with 4.5 KB of LDS padding (22 blocks =
 // 5.5 waves per SIMD resident, against 6 by registers) beat 256-thread blocks at every size
 // measured: 1M x 64 B 22.2 -> 21.5 us, 16M x 64 B 321 -> 313 us, 128 B 49.8 -> 49.3 us
 // (profiles/r02/lane_ab/: fewer frame bytes in flight per CU stream faster
-// from HBM; occupancy 8 (LATER 4: 60 VGPRs) was 2-8 % slower, 4 waves 2-9 % slower).
-#ifndef HALO_RX_LANE_BLOCK
-#define HALO_RX_LANE_BLOCK 64
-#endif
-#ifndef HALO_RX_LANE_LATER
-#define HALO_RX_LANE_LATER HALO_RX_LATER_CHUNKS
-#endif
-// A/B knobs: dynamic LDS bytes per lane-kernel block (caps resident blocks per CU, i.e. the
-// frame bytes in flight), and XCD-contiguous block order (blocks b, b+8, ... share an XCD; with
-// the remap each XCD's blocks take one contiguous range of the batch).
-#ifndef HALO_RX_LANE_LDS_PAD
-#define HALO_RX_LANE_LDS_PAD 4608
-#endif
-#ifndef HALO_RX_LANE_XCD
-#define HALO_RX_LANE_XCD 0
-#endif
-template <int LAYOUT, int FUSE, int ST>
-__device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t base, uint32_t lane, FrameState<1>& st,
-                                                   uint4* s_rec_w, Hist& hist) {
-    const bool compact = (p.flags & HALO_RX_RECORD_COMPACT) != 0;
-    const uint32_t i = base + lane;
-    frame_finish<1, FUSE, HALO_RX_LANE_LATER, kRound0<1>, kL3<LAYOUT>>(p, i, i < p.n, 0, lane, st, hist,
-                                                                     &s_rec_w[compact ? lane : 2 * lane]);
-    lane_window_store<ST>(p, base, lane, s_rec_w);
-}
+// from HBM; occupancy 8 (4 later chunks: 60 VGPRs) was 2-8 % slower, 4 waves 2-9 % slower).
+constexpr uint32_t kLaneBlock = 64;
+// Dynamic LDS bytes per lane-kernel block: caps resident blocks per CU, i.e. the frame bytes in flight.
+constexpr uint32_t kLaneLdsPad = 4608;
+// Tried (in git history up to 9ac2a89): prefetching the next window's address/length in waves that
+// loop: no gain at 1M (22.0 vs 22.1 us) and 3 % slower at 16M; with capped grids 2-11 % slower
+// (profiles/r02/ab_lane_prefetch.log). XCD-contiguous block order (blocks b, b+8, ... share an XCD;
+// with the remap each XCD's blocks took one contiguous range of the batch): rejected.
 
-// HALO_RX_LANE_LEAN: a launch that keeps no status histogram (p.hist null, the
+// The lean instance: a launch that keeps no status histogram (p.hist null, the
 // headline call) runs an instance with HIST false: no s_hist and no block barrier, no hist_open /
 // flush_hist, and p.hist a null constant wherever the window code tests it, so lane_fast_record and
 // frame_store carry no counting. That instance also drops amdgpu_num_sgpr(80): SGPRs do not limit
@@ -946,70 +893,37 @@ __device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t b
 // v_readlane pairs. Its dynamic LDS grows by the bytes of the s_hist it lacks, so both instances
 // allocate the same total per block and the resident blocks per CU do not change. Five interleaved
 // rounds against the parent (profiles/r10/ab_span_lean.log): 1M x 64 B 18.74-18.91 -> 18.39-18.63 us,
-// 4M 72.85-73.56 -> 72.13-72.97, 16M 279.9-282.7 -> 278.8-282.4. 0: every launch runs rx_lane_kernel.
-#ifndef HALO_RX_LANE_LEAN
-#define HALO_RX_LANE_LEAN 1
-#endif
+// 4M 72.85-73.56 -> 72.13-72.97, 16M 279.9-282.7 -> 278.8-282.4
+// (tried: every launch through rx_lane_kernel; in git history up to 9ac2a89).
 constexpr uint32_t kLaneHistLds = sizeof(uint32_t) * HALO_RX_STATUS_COUNT;
-constexpr uint32_t lane_dyn_lds(bool hist) { return HALO_RX_LANE_LDS_PAD + (hist ? 0u : kLaneHistLds); }
+constexpr uint32_t lane_dyn_lds(bool hist) { return kLaneLdsPad + (hist ? 0u : kLaneHistLds); }
 
 template <int LAYOUT, int FUSE>
-__global__ void __launch_bounds__(HALO_RX_LANE_BLOCK) __attribute__((amdgpu_num_sgpr(80)))
-#if HALO_RX_LANE_WAVES
-__attribute__((amdgpu_waves_per_eu(HALO_RX_LANE_WAVES)))
-#endif
+__global__ void __launch_bounds__(kLaneBlock) __attribute__((amdgpu_num_sgpr(80)))
 rx_lane_kernel(const RxParams p) {
     __shared__ uint32_t s_hist[HALO_RX_STATUS_COUNT];
-    __shared__ uint4 s_rec[HALO_RX_LANE_BLOCK / 64][128];  // per wave: 64 records of 32 B
+    __shared__ uint4 s_rec[kLaneBlock / 64][128];  // per wave: 64 records of 32 B
     if (threadIdx.x < HALO_RX_STATUS_COUNT) s_hist[threadIdx.x] = 0;
     __syncthreads();
     Hist hist = hist_open(p, s_hist);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w = threadIdx.x >> 6;
-#if HALO_RX_LANE_XCD
-    const uint32_t nb = gridDim.x, per = nb >> 3, rem = nb & 7u, xcd = blockIdx.x & 7u;
-    const uint32_t lblock = (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per) + (blockIdx.x >> 3);
-    const uint32_t wave = (lblock * blockDim.x + threadIdx.x) >> 6;
-#else
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-#endif
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
-#if HALO_RX_LANE_PREFETCH
-    // the next group's address and length load while this group is parsed (waves that loop)
-    FrameState<1> nx;
-    frame_meta<LAYOUT>(p, wave * 64 + lane, wave * 64 + lane < p.n, nx);
-#endif
     for (uint32_t base = wave * 64; base < p.n; base += nwaves * 64) {
-#if HALO_RX_LANE_PREFETCH
-        const uint32_t i = base + lane;
-        FrameState<1> st;
-        st.frame = nx.frame; st.L = nx.L; st.ndw = nx.ndw;
-        frame_loads<1>(0, st);
-        frame_meta<LAYOUT>(p, i + nwaves * 64, i + nwaves * 64 < p.n, nx);
-        lane_window_finish<LAYOUT, FUSE, kStoreLane>(p, base, lane, st, s_rec[w], hist);
-#else
         // A 16M-frame launch is bound by memory and ran 2 % slower with the fast path (waves that
         // finish sooner put more requests in flight), 4M 3 % and 1M 14 % faster:
-        // launches of up to HALO_RX_LANE_FAST_MAX_WAVES waves only.
-#if HALO_RX_LANE_FAST
-        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= HALO_RX_LANE_FAST_MAX_WAVES);
-#else
-        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist);
-#endif
-#endif
+        // launches of up to kLaneFastMaxWaves waves only.
+        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= kLaneFastMaxWaves);
     }
     flush_hist(p, hist);
 }
 
-// rx_lane_kernel for a launch without a histogram (HALO_RX_LANE_LEAN, above): the same windows
-// from the same waves. (The rejected knobs HALO_RX_LANE_XCD and _PREFETCH are not repeated here.)
+// rx_lane_kernel for a launch without a histogram (the lean instance, above): the same windows
+// from the same waves.
 template <int LAYOUT, int FUSE>
-__global__ void __launch_bounds__(HALO_RX_LANE_BLOCK)
-#if HALO_RX_LANE_WAVES
-__attribute__((amdgpu_waves_per_eu(HALO_RX_LANE_WAVES)))
-#endif
-rx_lane_lean_kernel(const RxParams p_in) {
-    __shared__ uint4 s_rec[HALO_RX_LANE_BLOCK / 64][128];
+__global__ void __launch_bounds__(kLaneBlock) rx_lane_lean_kernel(const RxParams p_in) {
+    __shared__ uint4 s_rec[kLaneBlock / 64][128];
     RxParams p = p_in;
     p.hist = nullptr;  // a constant for the window code: no counting is compiled in
     Hist hist{nullptr, 0, 0};
@@ -1018,11 +932,7 @@ rx_lane_lean_kernel(const RxParams p_in) {
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t nwaves = (gridDim.x * blockDim.x) >> 6;
     for (uint32_t base = wave * 64; base < p.n; base += nwaves * 64) {
-#if HALO_RX_LANE_FAST
-        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= HALO_RX_LANE_FAST_MAX_WAVES);
-#else
-        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist);
-#endif
+        lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= kLaneFastMaxWaves);
     }
 }
 
@@ -1045,10 +955,10 @@ struct MultiParams {
     halo_rx_result_t* out[kMultiMax];
 };
 
-template <int LAYOUT, bool HIST = true>  // HIST false: the launch keeps no histogram (HALO_RX_LANE_LEAN)
-__global__ void __launch_bounds__(HALO_RX_LANE_BLOCK) rx_lane_multi_kernel(const MultiParams mp) {
+template <int LAYOUT, bool HIST = true>  // HIST false: the launch keeps no histogram (the lean instance)
+__global__ void __launch_bounds__(kLaneBlock) rx_lane_multi_kernel(const MultiParams mp) {
     __shared__ uint32_t s_hist[HALO_RX_STATUS_COUNT];
-    __shared__ uint4 s_rec[HALO_RX_LANE_BLOCK / 64][128];
+    __shared__ uint4 s_rec[kLaneBlock / 64][128];
     RxParams lean;
     if constexpr (HIST) {
         if (threadIdx.x < HALO_RX_STATUS_COUNT) s_hist[threadIdx.x] = 0;
@@ -1074,24 +984,18 @@ __global__ void __launch_bounds__(HALO_RX_LANE_BLOCK) rx_lane_multi_kernel(const
         p.out = mp.out[b];
         p.n = mp.n[b];
         const uint32_t base = (win - (b ? mp.win_end[b - 1] : 0u)) * 64u;
-#if HALO_RX_LANE_FAST
-        lane_window<LAYOUT, 0, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= HALO_RX_LANE_FAST_MAX_WAVES);
-#else
-        lane_window<LAYOUT, 0, kStoreLane>(p, base, lane, s_rec[w], hist);
-#endif
+        lane_window<LAYOUT, 0, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= kLaneFastMaxWaves);
     }
     if constexpr (HIST) flush_hist(p0, hist);
 }
 
 template <int LAYOUT>
 void launch_lane_multi(const MultiParams& mp, dim3 grid, hipStream_t s) {
-    if constexpr (HALO_RX_LANE_LEAN) {
-        if (!mp.p.hist) {
-            hipLaunchKernelGGL((rx_lane_multi_kernel<LAYOUT, false>), grid, dim3(HALO_RX_LANE_BLOCK), lane_dyn_lds(false), s, mp);
-            return;
-        }
+    if (!mp.p.hist) {
+        hipLaunchKernelGGL((rx_lane_multi_kernel<LAYOUT, false>), grid, dim3(kLaneBlock), lane_dyn_lds(false), s, mp);
+        return;
     }
-    hipLaunchKernelGGL((rx_lane_multi_kernel<LAYOUT, true>), grid, dim3(HALO_RX_LANE_BLOCK), lane_dyn_lds(true), s, mp);
+    hipLaunchKernelGGL((rx_lane_multi_kernel<LAYOUT, true>), grid, dim3(kLaneBlock), lane_dyn_lds(true), s, mp);
 }
 
 // The resident small-poll consumer (RingServiceCtl, halo_common.h), kSvcGroups workgroups of
@@ -1209,18 +1113,11 @@ __global__ void __launch_bounds__(64 * kSvcWaves) ring_service_kernel(RingServic
 }
 
 // G lanes per frame (G in {4, 8, 16}); VGPR-limited occupancy, so no SGPR cap.
-#ifndef HALO_RX_GROUP_WAVES
-#define HALO_RX_GROUP_WAVES 5
-#endif
-// A/B knobs: threads per block and dynamic LDS padding per block (caps resident blocks per CU).
-#ifndef HALO_RX_GROUP_BLOCK
-#define HALO_RX_GROUP_BLOCK 256
-#endif
-#ifndef HALO_RX_GROUP_LDS_PAD
-#define HALO_RX_GROUP_LDS_PAD 0
-#endif
+// (Tried: other block sizes and dynamic LDS padding to cap the resident blocks per CU; in git
+// history up to 9ac2a89.)
+constexpr uint32_t kGroupBlock = 256, kGroupWaves = 5;
 template <int G, int LAYOUT, int FUSE>
-__global__ void __launch_bounds__(HALO_RX_GROUP_BLOCK) __attribute__((amdgpu_waves_per_eu(HALO_RX_GROUP_WAVES)))
+__global__ void __launch_bounds__(kGroupBlock) __attribute__((amdgpu_waves_per_eu(kGroupWaves)))
 rx_group_kernel(const RxParams p) {
     static_assert(G == 4 || G == 8 || G == 16, "G must be 4, 8 or 16");
     group_kernel_body<G, LAYOUT, FUSE>(p);
@@ -1232,39 +1129,24 @@ rx_group_kernel(const RxParams p) {
 // the uniform sweep found best for that size: <= 128 B (and frames failing the length check)
 // lane per frame, <= 1024 B 4 lanes, <= 4096 B 8 lanes, longer 16 lanes. Every pass keeps all
 // groups busy with frames of one class, so no lane waits behind a longer neighbour.
-#ifndef HALO_RX_MIX_WINDOW
-#define HALO_RX_MIX_WINDOW 256
-#endif
-constexpr uint32_t kMixWindow = HALO_RX_MIX_WINDOW;  // frames per wave window (a multiple of 64)
+constexpr uint32_t kMixWindow = 256;                 // frames per wave window (a multiple of 64)
 constexpr int kMixPer = (int)(kMixWindow / 64);      // frames per lane in the classification
-#ifndef HALO_RX_MIX_MAX_G
-#define HALO_RX_MIX_MAX_G 16  // 8: frames > 4096 B take the 8-lane pass (no 16-lane pass compiled)
-#endif
+// (Tried: frames > 4096 B on the 8-lane pass, no 16-lane pass compiled; in git history up to 9ac2a89.)
 
 // Later-round chunks per lane in the mix passes: just enough for each class's size range in one
 // later round trip (<= 128 B: 64 + 4*16 B; 570 B on 4 lanes: 256 + 5*64 B; 1500 B on 8 lanes:
 // 512 + 8*128 B), so the short classes' passes do not hold the buffers the long ones need.
 // IMIX 1.60 -> 1.58 ms, 570 B 150 -> 147 us (profiles/r01/ab_r43_mix_later_small.log, 5 vs 6
-// chunks for 570 B: ab_r43_mix_later_g4.log).
-#ifndef HALO_RX_MIX_LATER_SMALL
-#define HALO_RX_MIX_LATER_SMALL 1
-#endif
-#ifndef HALO_RX_MIX_LATER_G4
-#define HALO_RX_MIX_LATER_G4 5
-#endif
+// chunks for 570 B: ab_r43_mix_later_g4.log; tried: kLaterChunks for every class; in git history
+// up to 9ac2a89).
 template <int G>
-constexpr int kMixLater = !HALO_RX_MIX_LATER_SMALL ? HALO_RX_LATER_CHUNKS
-                        : G == 1 ? 4 : G == 4 ? HALO_RX_MIX_LATER_G4 : HALO_RX_LATER_CHUNKS;
+constexpr int kMixLater = G == 1 ? 4 : G == 4 ? 5 : kLaterChunks;
 
-// Round-0 chunks per lane in the mix passes (HALO_RX_MIX_ROUND0=1): 570 B on 4 lanes in one round
-// trip (9 x 64 B >= 576 B), 1500 B on 8 lanes in one (12 x 128 B >= 1536 B). Off: the bigger round
-// 0 spills at occupancy 4 (IMIX 2.06 ms) and at occupancy 3 is slower still than two round trips
-// (IMIX 1.69 ms, 570 B 173 us; profiles/r01/ab_r43_mix_round0_rejected.log).
-#ifndef HALO_RX_MIX_ROUND0
-#define HALO_RX_MIX_ROUND0 0
-#endif
-template <int G>
-constexpr int kMixRound0 = !HALO_RX_MIX_ROUND0 ? kRound0<G> : G == 4 ? 9 : G == 8 && HALO_RX_MIX_ROUND0 >= 2 ? 12 : kRound0<G>;
+// Round 0 of the mix passes is kRound0 chunks per lane, as everywhere. Tried: 570 B on 4 lanes in
+// one round trip (9 x 64 B >= 576 B), 1500 B on 8 lanes in one (12 x 128 B >= 1536 B): the bigger
+// round 0 spills at occupancy 4 (IMIX 2.06 ms) and at occupancy 3 is slower still than two round
+// trips (IMIX 1.69 ms, 570 B 173 us; profiles/r01/ab_r43_mix_round0_rejected.log; in git history up
+// to 9ac2a89).
 
 template <int G, int FUSE, bool L3>
 __device__ __forceinline__ void mix_pass(const RxParams& p, uint32_t e_begin, uint32_t e_end, uint32_t lane,
@@ -1276,20 +1158,17 @@ __device__ __forceinline__ void mix_pass(const RxParams& p, uint32_t e_begin, ui
     for (uint32_t e0 = e_begin; e0 < e_end; e0 += FPW) {
         const uint32_t e = e0 + lane / G;
         const bool has = e < e_end;
-        FrameState<G, kMixRound0<G>> st;
+        FrameState<G> st;
         st.frame = has ? reinterpret_cast<const uint8_t*>(s_ptr[e]) : p.bytes;
         st.L = has ? s_len[e] : 0u;
         st.ndw = (has && st.L >= (L3 ? 20u : kEthMin) && st.L <= len_max) ? (st.L + 3) >> 2 : 0;
         frame_loads(gl, st);
-        frame_finish<G, FUSE, kMixLater<G>, kMixRound0<G>, L3>(p, has ? s_idx[e] : 0u, has, gl, grp_base, st, hist);
+        frame_finish<G, FUSE, kMixLater<G>, kRound0, L3>(p, has ? s_idx[e] : 0u, has, gl, grp_base, st, hist);
     }
 }
 
 template <int LAYOUT, int FUSE>
-#ifndef HALO_RX_MIX_WAVES
-#define HALO_RX_MIX_WAVES 4
-#endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HALO_RX_MIX_WAVES))) rx_mix_kernel(const RxParams p) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) rx_mix_kernel(const RxParams p) {
     __shared__ uint32_t s_hist[HALO_RX_STATUS_COUNT];
     __shared__ uint64_t s_ptr[4][kMixWindow];
     __shared__ uint32_t s_idx[4][kMixWindow];
@@ -1316,7 +1195,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HALO_R
             if (i < p.n) frame_at<LAYOUT>(p, i, fp[k], fl[k]);
             cls[k] = i >= p.n ? 4u
                    : (fl[k] <= 128 || fl[k] > len_max) ? 0u
-                   : fl[k] <= 1024 ? 1u : (HALO_RX_MIX_MAX_G < 16 || fl[k] <= 4096) ? 2u : 3u;
+                   : fl[k] <= 1024 ? 1u : fl[k] <= 4096 ? 2u : 3u;
         }
         // counting sort by class: one ballot live at a time
         uint32_t pos[kMixPer];
@@ -1348,8 +1227,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HALO_R
         mix_pass<1, FUSE, L3>(p, st0, st1, lane, s_ptr[w], s_idx[w], s_len[w], len_max, hist);
         mix_pass<4, FUSE, L3>(p, st1, st2, lane, s_ptr[w], s_idx[w], s_len[w], len_max, hist);
         mix_pass<8, FUSE, L3>(p, st2, st3, lane, s_ptr[w], s_idx[w], s_len[w], len_max, hist);
-        if constexpr (HALO_RX_MIX_MAX_G >= 16)
-            mix_pass<16, FUSE, L3>(p, st3, nall, lane, s_ptr[w], s_idx[w], s_len[w], len_max, hist);
+        mix_pass<16, FUSE, L3>(p, st3, nall, lane, s_ptr[w], s_idx[w], s_len[w], len_max, hist);
         __builtin_amdgcn_wave_barrier();
     }
     flush_hist(p, hist);
@@ -1427,9 +1305,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 // down to it). Measured and removed (profiles/r02/stream/stream1-3.log): software-pipelining the
 // step loads (+16 VGPRs: 570 B 132 -> 156 us), issuing the next step's loads before this step's
 // lookups, and prefetching the next window's addresses / headers (neutral or slower).
-#ifndef HALO_RX_STREAM_ALIGN
-#define HALO_RX_STREAM_ALIGN 128
-#endif
+constexpr uint32_t kStreamAlign = 128;
 
 // This lane's 64 bytes of the step at s0 (sub-chunk u at s0 + 1024u + 16 lane, so each load
 // instruction reads 1 KB contiguous): always four 16-byte loads, no branch, so the load counter
@@ -1473,22 +1349,10 @@ __device__ __forceinline__ bool window_pages_covered(bool in, uint32_t ps, uint3
     return true;
 }
 
-// A/B knobs: threads per block and dynamic LDS padding per block.
-#ifndef HALO_RX_STREAM_BLOCK
-#define HALO_RX_STREAM_BLOCK 256
-#endif
-#ifndef HALO_RX_STREAM_LDS_PAD
-#define HALO_RX_STREAM_LDS_PAD 0
-#endif
-#ifndef HALO_RX_STREAM_WAVES
-#define HALO_RX_STREAM_WAVES 6
-#endif
-#ifndef HALO_RX_STREAM_PIPE  // 1: the next step's loads issued before this step is summed
-#define HALO_RX_STREAM_PIPE 0
-#endif
-#ifndef HALO_RX_STREAM_HDR
-#define HALO_RX_STREAM_HDR 1
-#endif
+// Threads per block and waves per EU of the stream kernel. (Tried: dynamic LDS padding per block
+// for uniform batches, the next step's loads issued before this step is summed, and every call on
+// the instance without HDR; in git history up to 9ac2a89.)
+constexpr int kStreamBlock = 256, kStreamWaves = 6;
 
 // One stream step's 64 bytes of this lane: their 16-byte sub-chunk prefixes (P at each sub-chunk
 // start; carry = P at the step start) and the bytes, to the wave's LDS.
@@ -1518,14 +1382,10 @@ __device__ __forceinline__ void stream_sum(const uint32_t (&x)[4][4], uint32_t l
 // Mixed-size batches (IMIX) take the stream kernel in one-wave blocks with 1.5 KB of LDS padding
 // (22 blocks = 5.5 waves per SIMD resident): IMIX 1.27 -> 1.25 ms; uniform batches keep 256-thread
 // blocks, which the 570 B line prefers (127 vs 133 us; profiles/r02/ab_stream_group_block_uncapped.log).
-#ifndef HALO_RX_STREAM_MIXED_BLOCK
-#define HALO_RX_STREAM_MIXED_BLOCK 64
-#endif
-#ifndef HALO_RX_STREAM_MIXED_LDS_PAD
-#define HALO_RX_STREAM_MIXED_LDS_PAD 1536
-#endif
-template <int LAYOUT, int FUSE, bool HDR, int BLK = HALO_RX_STREAM_BLOCK>
-__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(HALO_RX_STREAM_WAVES)))
+constexpr int kStreamMixedBlock = 64;
+constexpr uint32_t kStreamMixedLdsPad = 1536;
+template <int LAYOUT, int FUSE, bool HDR, int BLK = kStreamBlock>
+__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(kStreamWaves)))
 rx_stream_kernel(const RxParams p) {
     constexpr int kW = BLK / 64;
     __shared__ uint32_t s_hist[HALO_RX_STATUS_COUNT];
@@ -1572,7 +1432,7 @@ rx_stream_kernel(const RxParams p) {
                 const uint32_t lo = wave_allreduce(rd ? ps : kNone, umin);
                 const uint32_t hi = wave_allreduce(rd ? ps + 4 * st.ndw : 0u, umax);
                 const uint32_t sum = wave_allreduce(rd ? st.L : 0u, uadd);
-                const uint32_t G0 = lo & ~(uint32_t)(HALO_RX_STREAM_ALIGN - 1);
+                const uint32_t G0 = lo & ~(kStreamAlign - 1);
                 const uint32_t span = hi - G0;
                 if (!__ballot(rd && d64 >= (1ull << 31)) && span <= 2 * sum + 8192u &&
                     window_pages_covered(rd, ps, 4 * st.ndw, lo, hi, (uint32_t)B & 4095u)) {
@@ -1582,25 +1442,11 @@ rx_stream_kernel(const RxParams p) {
                     uint32_t pb = kNone;  // the segment's last byte, once the total length has passed
                     uint32_t PA = 0, PB = 0, carry = 0;
                     const uint32_t nsteps = (span + kStreamStep - 1) / kStreamStep;
-#if HALO_RX_STREAM_PIPE
-                    uint32_t x[4][4];
-                    stream_load(B, G0, lane, lo, hi, x);
-#endif
                     for (uint32_t t = 0; t < nsteps; ++t) {
                         const uint32_t s0 = G0 + t * kStreamStep;
-#if HALO_RX_STREAM_PIPE
-                        uint32_t xn[4][4];  // the next step's bytes (past the window: a clamped re-read)
-                        stream_load(B, s0 + kStreamStep, lane, lo, hi, xn);
-                        stream_sum(x, lane, carry, s_base[w], s_x[w]);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) x[u][k] = xn[u][k];
-#else
                         uint32_t x[4][4];
                         stream_load(B, s0, lane, lo, hi, x);
                         stream_sum(x, lane, carry, s_base[w], s_x[w]);
-#endif
                         const uint32_t* xw = reinterpret_cast<const uint32_t*>(s_x[w]);
                         const uint32_t r0 = ps - s0;  // header start in this step (wraps below it)
                         if (__ballot(rd && (r0 < kStreamStep || r0 + 48u < 48u + kStreamStep))) {
@@ -1648,32 +1494,18 @@ rx_stream_kernel(const RxParams p) {
                 const uint32_t lo = wave_allreduce(seg ? ps : kNone, umin);
                 const uint32_t hi = wave_allreduce(seg ? ps + 4 * st.ndw : 0u, umax);
                 const uint32_t sum = wave_allreduce(seg ? v.seg_end - kSeg : 0u, uadd);
-                const uint32_t G0 = S & ~(uint32_t)(HALO_RX_STREAM_ALIGN - 1);
+                const uint32_t G0 = S & ~(kStreamAlign - 1);
                 const uint32_t span = E - G0;
                 if (!__ballot(seg && d64 >= (1ull << 31)) && span <= 2 * sum + 8192u &&
                     window_pages_covered(seg, ps, 4 * st.ndw, lo, hi, (uint32_t)B & 4095u)) {
                     uint32_t PA = 0, PB = 0, carry = 0;
                     const uint32_t ea = pe - 1;  // the segment's last byte
                     const uint32_t nsteps = (span + kStreamStep - 1) / kStreamStep;
-#if HALO_RX_STREAM_PIPE
-                    uint32_t x[4][4];
-                    stream_load(B, G0, lane, lo, hi, x);
-#endif
                     for (uint32_t t = 0; t < nsteps; ++t) {
                         const uint32_t s0 = G0 + t * kStreamStep;
-#if HALO_RX_STREAM_PIPE
-                        uint32_t xn[4][4];  // the next step's bytes (past the window: a clamped re-read)
-                        stream_load(B, s0 + kStreamStep, lane, lo, hi, xn);
-                        stream_sum(x, lane, carry, s_base[w], s_x[w]);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) x[u][k] = xn[u][k];
-#else
                         uint32_t x[4][4];
                         stream_load(B, s0, lane, lo, hi, x);
                         stream_sum(x, lane, carry, s_base[w], s_x[w]);
-#endif
                         const uint32_t ra = pa - s0, rb = ea - s0;
                         if (seg && ra < kStreamStep) PA = stream_prefix(s_base[w], s_x[w], ra, ra & 3u);
                         if (seg && rb < kStreamStep) PB = stream_prefix(s_base[w], s_x[w], rb, (rb & 3u) + 1u);
@@ -1714,23 +1546,15 @@ rx_stream_kernel(const RxParams p) {
 // and a looping wave serialises its round trips: lifting it took 16M x 64 B 314 -> 294 us,
 // 128M x 64 B 2.74 -> 2.32 ms, IMIX 1.32 -> 1.28 ms, jumbo 6.20 -> 6.14 ms, 1500 B within noise
 // (profiles/r02/ab_grid_cap_raised.log).
-#ifndef HALO_RX_MAX_BLOCKS
-#define HALO_RX_MAX_BLOCKS 4194304ull
-#endif
-#ifndef HALO_RX_LANE_MAX_BLOCKS
-#define HALO_RX_LANE_MAX_BLOCKS HALO_RX_MAX_BLOCKS
-#endif
-#ifndef HALO_RX_HIST_HALVE_MAX  // lane-kernel grids up to this many blocks are halved when a histogram is kept
-#define HALO_RX_HIST_HALVE_MAX 16384u
-#endif
+constexpr uint64_t kMaxBlocks = 4194304ull;
+constexpr uint32_t kHistHalveMax = 16384u;  // lane-kernel grids up to this many blocks are halved when a histogram is kept
 constexpr int kVariantMix = -1, kVariantStream = 2, kVariantStreamMixed = 3;
 
-uint32_t grid_for(uint64_t n, uint32_t frames_per_wave, uint64_t max_blocks = HALO_RX_MAX_BLOCKS,
+uint32_t grid_for(uint64_t n, uint32_t frames_per_wave, uint64_t max_blocks = kMaxBlocks,
                   uint32_t waves_per_block = 4) {
     const uint64_t waves = (n + frames_per_wave - 1) / frames_per_wave;
     uint64_t blocks = (waves + waves_per_block - 1) / waves_per_block;
-    const uint64_t kMaxBlocks = max_blocks;
-    return (uint32_t)(blocks > kMaxBlocks ? kMaxBlocks : blocks);
+    return (uint32_t)(blocks > max_blocks ? max_blocks : blocks);
 }
 
 template <int LAYOUT, int FUSE = 0>
@@ -1738,52 +1562,48 @@ hipError_t launch_variant(const RxParams& p, int variant, hipStream_t s) {
     const dim3 block(256);
     switch (variant) {
         case 1: {
-            constexpr uint32_t wpb = HALO_RX_LANE_BLOCK / 64;
-            uint32_t grid = grid_for(p.n, 64, HALO_RX_LANE_MAX_BLOCKS * 4 / wpb, wpb);
+            constexpr uint32_t wpb = kLaneBlock / 64;
+            uint32_t grid = grid_for(p.n, 64, kMaxBlocks * 4 / wpb, wpb);
             // with a status histogram, batches up to 1M frames take half the waves, two frame groups
             // each: half the arrivals in the histogram tree, whose tail is a fixed cost per launch
             // (1M x 64 B: +2.1 instead of +2.7 us, 8192 blocks; 4096 gave no gain, profiles/r05/r5zm)
-            if (p.hist && grid <= HALO_RX_HIST_HALVE_MAX) grid = (grid + 1) / 2;
-            if constexpr (HALO_RX_LANE_LEAN) {
-                if (!p.hist) {
-                    hipLaunchKernelGGL((rx_lane_lean_kernel<LAYOUT, FUSE>), dim3(grid),
-                                       dim3(HALO_RX_LANE_BLOCK), lane_dyn_lds(false), s, p);
-                    break;
-                }
+            if (p.hist && grid <= kHistHalveMax) grid = (grid + 1) / 2;
+            if (!p.hist) {
+                hipLaunchKernelGGL((rx_lane_lean_kernel<LAYOUT, FUSE>), dim3(grid), dim3(kLaneBlock), lane_dyn_lds(false), s, p);
+                break;
             }
-            hipLaunchKernelGGL((rx_lane_kernel<LAYOUT, FUSE>), dim3(grid),
-                               dim3(HALO_RX_LANE_BLOCK), lane_dyn_lds(true), s, p);
+            hipLaunchKernelGGL((rx_lane_kernel<LAYOUT, FUSE>), dim3(grid), dim3(kLaneBlock), lane_dyn_lds(true), s, p);
             break;
         }
         case kVariantStream: {
-            constexpr uint32_t wpb = HALO_RX_STREAM_BLOCK / 64;
-            const dim3 g(grid_for(p.n, 64, HALO_RX_MAX_BLOCKS * 4 / wpb, wpb)), b(HALO_RX_STREAM_BLOCK);
-            if (HALO_RX_STREAM_HDR && (p.flags & HALO_RX_CSUM_ENABLE))
-                hipLaunchKernelGGL((rx_stream_kernel<LAYOUT, FUSE, true>), g, b, HALO_RX_STREAM_LDS_PAD, s, p);
+            constexpr uint32_t wpb = kStreamBlock / 64;
+            const dim3 g(grid_for(p.n, 64, kMaxBlocks * 4 / wpb, wpb)), b(kStreamBlock);
+            if (p.flags & HALO_RX_CSUM_ENABLE)
+                hipLaunchKernelGGL((rx_stream_kernel<LAYOUT, FUSE, true>), g, b, 0, s, p);
             else
-                hipLaunchKernelGGL((rx_stream_kernel<LAYOUT, FUSE, false>), g, b, HALO_RX_STREAM_LDS_PAD, s, p);
+                hipLaunchKernelGGL((rx_stream_kernel<LAYOUT, FUSE, false>), g, b, 0, s, p);
             break;
         }
         case kVariantStreamMixed: {
-            constexpr int BLK = HALO_RX_STREAM_MIXED_BLOCK;
+            constexpr int BLK = kStreamMixedBlock;
             constexpr uint32_t wpb = BLK / 64;
-            const dim3 g(grid_for(p.n, 64, HALO_RX_MAX_BLOCKS * 4 / wpb, wpb)), b(BLK);
-            if (HALO_RX_STREAM_HDR && (p.flags & HALO_RX_CSUM_ENABLE))
-                hipLaunchKernelGGL((rx_stream_kernel<LAYOUT, FUSE, true, BLK>), g, b, HALO_RX_STREAM_MIXED_LDS_PAD, s, p);
+            const dim3 g(grid_for(p.n, 64, kMaxBlocks * 4 / wpb, wpb)), b(BLK);
+            if (p.flags & HALO_RX_CSUM_ENABLE)
+                hipLaunchKernelGGL((rx_stream_kernel<LAYOUT, FUSE, true, BLK>), g, b, kStreamMixedLdsPad, s, p);
             else
-                hipLaunchKernelGGL((rx_stream_kernel<LAYOUT, FUSE, false, BLK>), g, b, HALO_RX_STREAM_MIXED_LDS_PAD, s, p);
+                hipLaunchKernelGGL((rx_stream_kernel<LAYOUT, FUSE, false, BLK>), g, b, kStreamMixedLdsPad, s, p);
             break;
         }
         case 4: case 8: case 16: {
-            constexpr uint32_t wpb = HALO_RX_GROUP_BLOCK / 64;
-            const dim3 b(HALO_RX_GROUP_BLOCK);
-            const uint64_t cap = HALO_RX_MAX_BLOCKS * 4 / wpb;
+            constexpr uint32_t wpb = kGroupBlock / 64;
+            const dim3 b(kGroupBlock);
+            const uint64_t cap = kMaxBlocks * 4 / wpb;
             if (variant == 4)
-                hipLaunchKernelGGL((rx_group_kernel<4, LAYOUT, FUSE>), dim3(grid_for(p.n, 16, cap, wpb)), b, HALO_RX_GROUP_LDS_PAD, s, p);
+                hipLaunchKernelGGL((rx_group_kernel<4, LAYOUT, FUSE>), dim3(grid_for(p.n, 16, cap, wpb)), b, 0, s, p);
             else if (variant == 8)
-                hipLaunchKernelGGL((rx_group_kernel<8, LAYOUT, FUSE>), dim3(grid_for(p.n, 8, cap, wpb)), b, HALO_RX_GROUP_LDS_PAD, s, p);
+                hipLaunchKernelGGL((rx_group_kernel<8, LAYOUT, FUSE>), dim3(grid_for(p.n, 8, cap, wpb)), b, 0, s, p);
             else
-                hipLaunchKernelGGL((rx_group_kernel<16, LAYOUT, FUSE>), dim3(grid_for(p.n, 4, cap, wpb)), b, HALO_RX_GROUP_LDS_PAD, s, p);
+                hipLaunchKernelGGL((rx_group_kernel<16, LAYOUT, FUSE>), dim3(grid_for(p.n, 4, cap, wpb)), b, 0, s, p);
             break;
         }
         default: hipLaunchKernelGGL((rx_mix_kernel<LAYOUT, FUSE>), dim3(grid_for(p.n, kMixWindow)), block, 0, s, p); break;
@@ -2112,8 +1932,8 @@ extern "C" HALO_API int halo_rx_parse_batches_device(const halo_rx_batch_desc_t*
     hipStream_t s = static_cast<hipStream_t>(stream);
     mp.p.hist_out = d_status_hist;
     if (d_status_hist && !(mp.p.hist = halo::hist_trees(halo::stream_device(s), s))) return HALO_E_NOMEM;
-    constexpr uint32_t wpb = HALO_RX_LANE_BLOCK / 64;
-    const dim3 grid(halo::grid_for(windows * 64u, 64, HALO_RX_LANE_MAX_BLOCKS * 4 / wpb, wpb));
+    constexpr uint32_t wpb = halo::kLaneBlock / 64;
+    const dim3 grid(halo::grid_for(windows * 64u, 64, halo::kMaxBlocks * 4 / wpb, wpb));
     if (flags & HALO_RX_L3_START)
         halo::launch_lane_multi<3>(mp, grid, s);
     else

@@ -292,24 +292,9 @@ __device__ __forceinline__ void build_frame(const BuildParams& p, const Frame& f
 // v_alignbyte, sums it with four v_dot2 and stores it: no masks, no bounds, 32-bit chunk indices.
 // Head: chunks 0..3 (header | payload, both checksum fields) on lanes 0..3, and the last, partial
 // chunk on lane 4, through the masked path; the head chunks are stored once the L4 sum is known.
-#ifndef HALO_TXB_BIG_PATH
-#define HALO_TXB_BIG_PATH 1
-#endif
-#ifndef HALO_TXB_HEAD_EARLY  // build_big: the head / tail chunk loads issued with the body's
-#define HALO_TXB_HEAD_EARLY 0  // neutral: 0.194 / 0.195 against 0.190 / 0.195 ms (profiles/r04/r4z)
-#endif
-#ifndef HALO_TXB_BIG_NB  // a chunk's fifth source dword from the neighbour lane (ds_bpermute)
-#define HALO_TXB_BIG_NB 1
-#endif
-#ifndef HALO_TXB_BIG_UNALIGNED  // body chunks as byte-unaligned 16-byte loads instead of aligned + v_alignbyte
-#define HALO_TXB_BIG_UNALIGNED 0
-#endif
-#ifndef HALO_TXB_NT_LD  // body payload loads non-temporal (read once)
-#define HALO_TXB_NT_LD 0
-#endif
-#ifndef HALO_TXB_NT_ST  // body frame stores non-temporal (written once)
-#define HALO_TXB_NT_ST 0
-#endif
+// Tried (in git history up to 9ac2a89, no measurement kept in the source): G >= 16 through
+// build_frame instead, every chunk loading its own fifth dword, body chunks as byte-unaligned
+// 16-byte loads, non-temporal body loads and stores.
 template <int G, int U>
 __device__ __forceinline__ void build_big(const BuildParams& p, const Frame& f, const uint32_t* hdr, uint32_t j,
                                           uint8_t* out) {
@@ -320,45 +305,27 @@ __device__ __forceinline__ void build_big(const BuildParams& p, const Frame& f, 
     const uint64_t P = f.pay - f.hdr_end;  // the source address of frame byte 0's position
     const uint32_t sh = (uint32_t)(P & 3u);
     const uint32_t cb_end = pay_end >> 4;  // chunks [4, cb_end): payload bytes only
-    typedef const __attribute__((address_space(1), unused)) uint32_t gu32_t;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4), unused));
+    typedef const __attribute__((address_space(1))) uint32_t gu32_t;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
     uint32_t sum = 0;
-    // the head / tail chunk of lanes 0..4 (masked path below): its loads go out with the body's,
-    // one memory round trip per frame instead of two (HALO_TXB_HEAD_EARLY)
+    // the head / tail chunk of lanes 0..4 (masked path below), loaded after the body. Tried: its loads
+    // issued with the body's, one memory round trip per frame instead of two. Neutral: 0.194 / 0.195
+    // against 0.190 / 0.195 ms (profiles/r04/r4z; in git history up to 9ac2a89)
     const uint32_t c = j < 4 ? j : cb_end;
     const bool mine = j < 4 ? 4 * j < ndw : (j == 4 && cb_end >= 4 && 4 * cb_end < ndw);
-    uint32_t hraw[5] = {0u, 0u, 0u, 0u, 0u};
-    if (HALO_TXB_HEAD_EARLY && mine && chunk_has_payload(f, c, ndw)) payload_raw(f, c, hraw);
     for (uint32_t c0 = 4 + j; c0 < cb_end; c0 += U * G) {
         uint32_t raw[U][5] = {};  // (a row past cb_end is offered to the neighbour lane, never used)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t c = c0 + u * G;
             if (c < cb_end) {
-#if HALO_TXB_BIG_UNALIGNED
-                // the chunk's 16 source bytes in one byte-unaligned load: no fifth dword, no merge
-                typedef uint32_t u32x4b __attribute__((ext_vector_type(4), aligned(1)));
-                const u32x4b v = *(const __attribute__((address_space(1))) u32x4b*)(P + 16ull * c);
-                raw[u][0] = v.x; raw[u][1] = v.y; raw[u][2] = v.z; raw[u][3] = v.w;
-                raw[u][4] = 0u;
-#else
                 gu32_t* q = (gu32_t*)((P + 16ull * c) & ~3ull);
-#if HALO_TXB_NT_LD
-                const u32x4 v = __builtin_nontemporal_load((const __attribute__((address_space(1))) u32x4*)q);
-#else
                 const u32x4 v = *(const __attribute__((address_space(1))) u32x4*)q;
-#endif
                 raw[u][0] = v.x; raw[u][1] = v.y; raw[u][2] = v.z; raw[u][3] = v.w;
-#if HALO_TXB_BIG_NB
                 // only a chunk whose successor no lane of this round loaded fetches its fifth dword
                 raw[u][4] = (sh && (c + 1 == cb_end || (j == G - 1 && u == U - 1))) ? q[4] : 0u;
-#else
-                raw[u][4] = sh ? q[4] : 0u;
-#endif
-#endif
             }
         }
-#if HALO_TXB_BIG_NB && !HALO_TXB_BIG_UNALIGNED
         // The fifth dword of chunk c is the first dword of chunk c + 1, which lane j + 1 loaded in
         // the same row (lane G - 1: lane 0's next row): one ds_bpermute per row instead of a
         // second global load per chunk. Lane 0 offers its next row's first dword (only lane G - 1
@@ -374,7 +341,6 @@ __device__ __forceinline__ void build_big(const BuildParams& p, const Frame& f, 
                 if (!(c + 1 == cb_end || (j == G - 1 && u == U - 1))) raw[u][4] = nb;
             }
         }
-#endif
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t c = c0 + u * G;
@@ -382,21 +348,16 @@ __device__ __forceinline__ void build_big(const BuildParams& p, const Frame& f, 
             uint32_t w[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                w[i] = HALO_TXB_BIG_UNALIGNED ? raw[u][i] : __builtin_amdgcn_alignbyte(raw[u][i + 1], raw[u][i], sh);
+                w[i] = __builtin_amdgcn_alignbyte(raw[u][i + 1], raw[u][i], sh);
                 sum = hsum_acc(w[i], sum);
             }
-#if HALO_TXB_NT_ST
-            typedef uint32_t u32x4s __attribute__((ext_vector_type(4), aligned(4)));
-            __builtin_nontemporal_store(u32x4s{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4s*>(out + 16ull * c));
-#else
             *reinterpret_cast<uint4*>(out + 16ull * c) = make_uint4(w[0], w[1], w[2], w[3]);
-#endif
         }
     }
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     if (mine) {
-        uint32_t* raw = hraw;
-        if (!HALO_TXB_HEAD_EARLY && chunk_has_payload(f, c, ndw)) payload_raw(f, c, hraw);
+        uint32_t raw[5] = {0u, 0u, 0u, 0u, 0u};
+        if (chunk_has_payload(f, c, ndw)) payload_raw(f, c, raw);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const uint32_t k = 4 * c + i;
@@ -458,7 +419,7 @@ __device__ __forceinline__ uint32_t prefix_mask(int32_t n) {
 // v_dot2 per dword. The caller stages o[] in LDS and the wave stores its frames cooperatively.
 // UNI: every active lane of the wave has the same header end, payload end and layout (one protocol,
 // one payload length: the common batch), so the byte masks and the checksum field's position are
-// computed once, in scalar registers (HALO_TXB_SMALL_UNIFORM).
+// computed once, in scalar registers.
 template <bool UNI>
 __device__ __forceinline__ void build_small(const BuildParams& p, const Frame& f, const uint32_t* hdr,
                                             const void* safe, uint32_t (&o)[16]) {
@@ -543,18 +504,8 @@ __device__ __forceinline__ uint32_t verdict(uint32_t d2, uint32_t d9, uint32_t s
 // descriptor i of the tile and decides it; the wave's ballot ranks the rejections; then the
 // wave builds the tile's frames 64 / G at a time, G lanes per frame, each group taking its
 // descriptor's dwords from the lane that holds them (ds_bpermute). No LDS, no barrier.
-#ifndef HALO_TXB_SMALL  // 1: frames <= 64 B on the branch-free lane path (build_small)
-#define HALO_TXB_SMALL 1
-#endif
-#ifndef HALO_TXB_SMALL_UNIFORM  // 1: build_small's masks in scalar registers when the wave agrees
-#define HALO_TXB_SMALL_UNIFORM 1
-#endif
-#ifndef HALO_TXB_DESC_PREFETCH
-#define HALO_TXB_DESC_PREFETCH 1  // 64 B: 24.9 / 24.7 us against 25.5 / 25.0 without (profiles/r05/r5zx)
-#endif
-#ifndef HALO_TXB_DESC_LDS  // G = 1: the tile's descriptors read coalesced, through LDS
-#define HALO_TXB_DESC_LDS 0  // measured slower: 64 B 30.2 / 30.5 us against 29.1 / 29.3 (profiles/r04/r4p)
-#endif
+// Tried (in git history up to 9ac2a89): G = 1 without build_small (frames <= 64 B through
+// build_frame) and build_small without its wave-uniform form (no measurement kept in the source).
 #ifndef HALO_TXB_G1_WAVES
 #define HALO_TXB_G1_WAVES 4
 #endif
@@ -572,14 +523,11 @@ constexpr uint32_t kSplit = G >= 16 ? HALO_TXB_SPLIT : 1;
 template <int G, int U>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G == 1 ? HALO_TXB_G1_WAVES : 4 * kSplit<G>)))
 tx_build_kernel(const BuildParams p) {
-#ifndef HALO_TXB_G1_LDS_TRIM
-#define HALO_TXB_G1_LDS_TRIM 1
-#endif
     // the descriptor staging is only for G > 1 (a lane per frame keeps its own): 11 KB less LDS
     // per block, so the lane-per-frame build fits eight blocks per CU
     constexpr uint32_t S = kSplit<G>, kOwn = kTile / S;  // waves per tile; frames each stages
-    constexpr uint32_t kDescDw = (G > 1 || !HALO_TXB_G1_LDS_TRIM) ? kOwn * 10 + 1 : 1;
-    constexpr uint32_t kMetaDw = (G > 1 || !HALO_TXB_G1_LDS_TRIM) ? kOwn : 1;
+    constexpr uint32_t kDescDw = G > 1 ? kOwn * 10 + 1 : 1;
+    constexpr uint32_t kMetaDw = G > 1 ? kOwn : 1;
     __shared__ uint32_t s_desc[kBlock / 64][kDescDw];  // per wave: its tile's descriptors
     __shared__ uint32_t s_meta[kBlock / 64][kMetaDw];
     // per wave: frame-layout header dwords 0..15 (G > 1); G = 1: a lane's header for a long frame,
@@ -608,8 +556,11 @@ tx_build_kernel(const BuildParams p) {
         }
     };
     // G = 1: the next tile's descriptors load while this tile builds (one dependent round trip
-    // fewer per tile; +10 VGPRs)
-    constexpr bool kPf = G == 1 && HALO_TXB_DESC_PREFETCH;
+    // fewer per tile; +10 VGPRs): 64 B 24.9 / 24.7 us against 25.5 / 25.0 without (profiles/r05/r5zx).
+    // Tried for G = 1: the tile's descriptors read coalesced through LDS, 320 consecutive 8-byte
+    // words instead of 64 words 40 B apart per load: slower, 64 B 30.2 / 30.5 us against 29.1 / 29.3
+    // (profiles/r04/r4p; both in git history up to 9ac2a89)
+    constexpr bool kPf = G == 1;
     uint32_t dn[10];
     if constexpr (kPf) load_desc(((blockIdx.x * kBlock + threadIdx.x) >> 6) * kTile + lane, dn);
     for (uint32_t tw = (blockIdx.x * kBlock + threadIdx.x) >> 6; tw < p.n_tiles * S; tw += nw) {
@@ -620,24 +571,6 @@ tx_build_kernel(const BuildParams p) {
 #pragma unroll
             for (int k = 0; k < 10; ++k) d[k] = dn[k];
             load_desc((t + nw) * kTile + lane, dn);
-        } else if constexpr (G == 1 && HALO_TXB_DESC_LDS) {
-            // the tile's 64 descriptors as 320 consecutive 8-byte words, lane l taking words l,
-            // l + 64, ... (each load instruction reads 512 contiguous bytes instead of 64 words 40 B
-            // apart), through the wave's header rows (free until the headers are written below)
-            const uint2* src = reinterpret_cast<const uint2*>(p.desc + first);
-            const uint32_t words = (p.n - first < kTile ? p.n - first : kTile) * 5u;
-            uint32_t* scratch = &s_hdr[wv][0];
-#pragma unroll
-            for (uint32_t k = 0; k < 5; ++k) {
-                const uint32_t w = 64u * k + lane;
-                const uint2 v = w < words ? src[w] : make_uint2(0u, 0u);
-                scratch[2 * w] = v.x;
-                scratch[2 * w + 1] = v.y;
-            }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int k = 0; k < 10; ++k) d[k] = scratch[10 * lane + k];
-            __builtin_amdgcn_wave_barrier();  // read before the header rows are written
         } else {
             load_desc(i, d);
         }
@@ -675,13 +608,13 @@ tx_build_kernel(const BuildParams p) {
             uint32_t staged = 0;
             if (mine >> 31) {
                 const Frame f = decode(d, p.payload);
-                if (HALO_TXB_SMALL && f.flen <= 64u) {
+                if (f.flen <= 64u) {
                     uint32_t o[16];
                     // (the lanes here: this tile's small frames; uniform over them in the common batch)
                     // (flen <= 64: hdr_end, plen and base < 256; proto sets the checksum field)
                     const uint32_t sig = f.hdr_end | (f.plen << 8) | (f.base << 16) | (f.proto << 24);
                     const uint32_t sig0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)sig);
-                    if (HALO_TXB_SMALL_UNIFORM && __builtin_amdgcn_ballot_w64(sig != sig0) == 0)
+                    if (__builtin_amdgcn_ballot_w64(sig != sig0) == 0)
                         build_small<true>(p, f, hv, p.desc + i, o);
                     else
                         build_small<false>(p, f, hv, p.desc + i, o);
@@ -739,7 +672,7 @@ tx_build_kernel(const BuildParams p) {
                     uint32_t dd[10];
 #pragma unroll
                     for (int k = 0; k < 10; ++k) dd[k] = s_desc[wv][10 * sl + k];
-                    if constexpr (G >= 16 && HALO_TXB_BIG_PATH)
+                    if constexpr (G >= 16)
                         build_big<G, U>(p, decode(dd, p.payload), &s_hdr[wv][kRow * sl], j,
                                         p.frames + (uint64_t)(first + fl) * p.stride);
                     else
@@ -768,22 +701,18 @@ tx_build_kernel(const BuildParams p) {
 #ifndef HALO_TXB_PAIR
 #define HALO_TXB_PAIR 1
 #endif
-#ifndef HALO_TXB_PAIR_XCD
-#define HALO_TXB_PAIR_XCD 1
-#endif
 template <int U>
 __global__ void __launch_bounds__(kBlock) tx_build_pair_kernel(const BuildParams p) {
     __shared__ uint32_t s_hdr[kBlock / 64][2 * 16];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    // XCD-aware order (HALO_TXB_PAIR_XCD): blocks are dealt round-robin over the 8 XCDs, and the 8
-    // blocks of a tile all read the tile's descriptor block — in dispatch order once per XCD, 1.19x
-    // the algorithmic reads (r4p). Within each run of 64 blocks (8 tiles), block b takes tile
+    // XCD-aware order: blocks are dealt round-robin over the 8 XCDs, and the 8 blocks of a tile all
+    // read the tile's descriptor block — in dispatch order (tried: lb = blockIdx.x) once per XCD,
+    // 1.19x the algorithmic reads (r4p). Within each run of 64 blocks (8 tiles), block b takes tile
     // b % 8 of the run, part (b / 8) % 8: a tile stays on one XCD, and the batch is still walked
-    // in order 8 tiles at a time. (Giving each XCD a contiguous eighth of the batch instead cut the
-    // reads to 1.0002x but ran 2-3 % slower: r4q.)
-    const uint32_t lb = HALO_TXB_PAIR_XCD == 2 ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3)
-                      : HALO_TXB_PAIR_XCD == 1 ? (blockIdx.x & ~63u) | ((blockIdx.x & 7u) << 3) | ((blockIdx.x >> 3) & 7u)
-                                               : blockIdx.x;
+    // in order 8 tiles at a time. (Tried: each XCD a contiguous eighth of the batch instead, lb =
+    // (b & 7) * (grid / 8) + b / 8, cut the reads to 1.0002x but ran 2-3 % slower: r4q. Both in git
+    // history up to 9ac2a89.)
+    const uint32_t lb = (blockIdx.x & ~63u) | ((blockIdx.x & 7u) << 3) | ((blockIdx.x >> 3) & 7u);
     const uint32_t pair = lb * (kBlock / 64) + wv;
     if (2ull * pair >= p.n) return;  // wave-uniform
     const uint32_t g = lane >> 5, j = lane & 31u;
@@ -972,10 +901,8 @@ extern "C" HALO_API int halo_tx_build_batch_device(const halo_tx_build_desc_t* d
     // Launch 2 (one word in the common case) costs the same with 1, 8 or 64 blocks (25.2 / 25.2 /
     // 25.0 us per 64 B call, profiles/r05/r5j): the gap between two dependent dispatches, not the
     // grid. 64 keeps the renumbering after a rejection wide.
-#ifndef HALO_TXB_FINISH_BLOCKS
-#define HALO_TXB_FINISH_BLOCKS 64u
-#endif
-    hipLaunchKernelGGL(halo::tx_finish_kernel, dim3(p.n_tiles < HALO_TXB_FINISH_BLOCKS ? p.n_tiles : HALO_TXB_FINISH_BLOCKS),
+    constexpr uint32_t kFinishBlocks = 64;
+    hipLaunchKernelGGL(halo::tx_finish_kernel, dim3(p.n_tiles < kFinishBlocks ? p.n_tiles : kFinishBlocks),
                        dim3(1024), 0, s, p);
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }

@@ -84,14 +84,15 @@ BOUNDARIES = {
     "txb_pair_grid": dict(kernels="tx_build_pair_kernel<3> (no grid-stride loop: grid = ceil(n / 512) * 64 blocks)",
                           file="tx_build.hip", constants=("txb_pair_run", "txb_pair_run_blocks", "txb_kBlock"),
                           first_past=None, test="test_tx_build_second_trip[pair]"),
-    # halo_xxh3_64_batch_device's short-string kernel: a wave scans kShortScan strings, a workgroup of
-    # four waves 4 * kShortScan, and blocks_for caps the grid at 16,384 workgroups: the second trip
-    # begins at 2^24 + 1 strings, beyond the 2^23 strings of <= 16 bytes a test may hold
-    "xxh3_short_trip": dict(kernels="xxh3_short_kernel", file="flow_hash.hip", constants=("blocks_for", "kShortScan"),
-                            first_past=16_777_217, test=None,
-                            out_of_reach="2^24 + 1 strings: above the 2^23 a test of this suite may hold"),
+    # halo_xxh3_64_batch_device launches xxh3_run_kernel alone: one 64-lane block per window of kRunWin
+    # strings, no grid-stride loop and no cap (grid = ceil(n / kRunWin)). No edge today; the named tests
+    # cross a window edge (20,000 strings: 79 windows, the last one 32 strings), and the launch
+    # expression is matched in read_constants so that a cap put on that grid meets a test.
+    "xxh3_run_grid": dict(kernels="xxh3_run_kernel (no grid-stride loop: grid = ceil(n / kRunWin) one-wave blocks)",
+                          file="flow_hash.hip", constants=("kRunWin",), first_past=None,
+                          test="tests/test_gpu_flow_hash.py::test_xxh3_random_batches_vs_oracle (n = 20,000), "
+                               "test_xxh3_canonical_every_length"),
 }
-XXH3_SHORT_REACH = 1 << 23
 
 
 def _product(expr: str) -> int:
@@ -141,6 +142,9 @@ def read_constants() -> dict:
     assert int(pair[0]) == int(pair[1]) - 1
     # the build launch's cap, and that the launch code applies it (times the waves per tile)
     _one(r"cap = HALO_TXB_MAX_BLOCKS \* split;\s*const dim3 grid\(blocks < cap \? blocks : cap\)", txb)
+    # the XXH3 launch: a block of one wave per window, the window being kRunWin, nothing else in the grid
+    _one(r"const uint32_t win = halo::kRunWin;\s*p\.win = win;\s*hipLaunchKernelGGL\(halo::xxh3_run_kernel, "
+         r"dim3\(\(n \+ win - 1\) / win\), dim3\(64\), 0, s, p\);", fh)
     return {
         "txb_g1_waves": int(_one(r"#define HALO_TXB_G1_WAVES (\d+)", txb)),
         "txb_blocks_per_wave": int(_one(r"#define HALO_TXB_MAX_BLOCKS \(HALO_TXB_G1_WAVES \* (\d+)u\)", txb)),
@@ -162,7 +166,7 @@ def read_constants() -> dict:
         "sw_pass": scan_pass("switch_fwd.hip", "sw_scan_kernel"),
         "kTile": int(_one(r"constexpr uint32_t kTile = (\d+);", sw)),
         "kGatherTile": int(_one(r"constexpr uint32_t kGatherTile = (\d+);", arp_h)),
-        "kShortScan": int(_one(r"#define HALO_XXH3_SHORT_SCAN (\d+)", fh)),
+        "kRunWin": int(_one(r"constexpr uint32_t kRunWin = (\d+);", fh)),
     }
 
 
@@ -179,6 +183,8 @@ def derived(c: dict) -> dict:
     txb_trip = txb_waves * c["txb_kTile"] + 1
     # the pair kernel's grid holds a wave for every pair of frames of every run: nothing to cross
     assert c["txb_pair_run_blocks"] * (c["txb_kBlock"] // 64) * 2 == c["txb_pair_run"]
+    # the XXH3 windows of the named tests' 20,000 strings: more than one, the last one partial
+    assert 20_000 > c["kRunWin"] and 20_000 % c["kRunWin"] and c["kRunWin"] % 64 == 0
     return {
         "txb_g1_trip": txb_trip,
         "txb_g4_trip": txb_trip,
@@ -201,7 +207,7 @@ def derived(c: dict) -> dict:
         "tx_g8_trip": c["tx_waves"] * (64 // 8) + 1,
         "tx_g4_trip": c["tx_waves"] * (64 // 4) + 1,
         "tx_g1_trip": c["tx_waves"] * 64 + 1,
-        "xxh3_short_trip": c["blocks_for"] * 4 * c["kShortScan"] + 1,
+        "xxh3_run_grid": None,
     }
 
 

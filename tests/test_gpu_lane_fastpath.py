@@ -1,4 +1,4 @@
-"""GPU: the lane kernel's fast path for windows of plain frames (HALO_RX_LANE_FAST, DESIGN.md
+"""GPU: the lane kernel's fast path for windows of plain frames (lane_window_fast, DESIGN.md
 §15.12) against the C oracle, bit-exact, at the smallest shapes where the split between the fast
 path and the general one can go wrong: whole and partial windows, one deviating frame at lane 0, 31
 or 63 of an otherwise plain window, failing checksums inside a fast window, every frame and segment

@@ -1,5 +1,5 @@
 """GPU: dense windows through the lane kernel's two instances (with a histogram, and the
-no-histogram instance of HALO_RX_LANE_LEAN) against the C oracle, bit-exact. The
+no-histogram instance rx_lane_lean_kernel) against the C oracle, bit-exact. The
 cases were written for the span read of a dense window (HALO_RX_LANE_SPAN: 64 back-to-back frames of
 61..64 bytes read as one 4096-byte span and transposed through LDS), which §15.13 measured and
 rejected; they hold whatever reads a dense window to the same bytes. The shapes are the smallest at

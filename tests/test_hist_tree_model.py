@@ -57,7 +57,7 @@ def test_tree_counts_exact_and_words_reset(g):
         assert all(v == 0 for v in l1.values()) and all(v == 0 for v in l2.values())
 
 
-RUN = 16  # HALO_HIST_RUNS
+RUN = 16  # kHistRuns (rx_parse.hip, flush_hist)
 
 
 def run_runs(counts: np.ndarray, order: np.ndarray, words: dict, out: np.ndarray) -> int:

@@ -16,7 +16,7 @@ def _term(lo, hi, s0, s1):
     return _mulfold(lo ^ s0, hi ^ s1)
 
 
-B = 8  # HALO_XXH3_RUN_B
+B = 8  # kRunB (flow_hash.hip)
 
 
 def run_cost(n: int) -> int:
