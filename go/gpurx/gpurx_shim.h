@@ -16,6 +16,14 @@ _Static_assert(offsetof(halo_rx_result_t, src_ip) == 8, "halo_rx_result_t.src_ip
 _Static_assert(offsetof(halo_rx_result_t, payload_off) == 20, "halo_rx_result_t.payload_off");
 _Static_assert(offsetof(halo_rx_result_t, l4_ack) == 28, "halo_rx_result_t.l4_ack");
 _Static_assert(sizeof(halo_rx_netif_t) == 16, "halo_rx_netif_t is 16 bytes");
+// deliver.go's DeliverHdr, DeliverSummary and DeliverIndex
+_Static_assert(sizeof(halo_deliver_hdr_t) == 24, "halo_deliver_hdr_t is 24 bytes");
+_Static_assert(offsetof(halo_deliver_hdr_t, remote_ip) == 8, "halo_deliver_hdr_t.remote_ip");
+_Static_assert(offsetof(halo_deliver_hdr_t, seq) == 16, "halo_deliver_hdr_t.seq");
+_Static_assert(sizeof(halo_deliver_summary_t) == 40, "halo_deliver_summary_t is 40 bytes");
+_Static_assert(offsetof(halo_deliver_summary_t, kind_counts) == 24, "halo_deliver_summary_t.kind_counts");
+_Static_assert(sizeof(halo_deliver_index_t) == 8, "halo_deliver_index_t is 8 bytes");
+_Static_assert(sizeof(halo_deliver_config_t) == 16, "halo_deliver_config_t is 16 bytes");
 
 // gpurx_netif: a halo_rx_netif_t from NetIf.MacAddr, IpAddrToU(NetIf.IpAddr), NatEnable.
 static inline halo_rx_netif_t gpurx_netif(const uint8_t* mac, uint32_t ip, int nat_enable) {

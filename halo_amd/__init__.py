@@ -8,6 +8,7 @@ from . import _lib  # noqa: F401  (raises if libhalo_rx.so is not built: no CPU 
 from ._lib import ACTION, ACTION_NAMES, RESULT_DTYPE, STATUS, STATUS_NAMES, NetIf, HaloError  # noqa: F401
 from ._lib import EGRESS_PORT_DTYPE  # noqa: F401
 from .arp import ArpTable  # noqa: F401
+from .deliver import DeliverResult, deliver, deliver_host, port_map  # noqa: F401
 from .egress import EgressResult, egress_arp, egress_host, egress_masks, egress_switch  # noqa: F401
 from .nat import NatTable  # noqa: F401
 from .respond import RespondResult, build_replies, respond, respond_host, tcp_port_map  # noqa: F401  (adds ArpTable.encap_tx)
@@ -16,4 +17,5 @@ from .pmflow import PortMappingFlowTable, forward_return_flows  # noqa: F401  (a
 
 __all__ = ["PortMappingFlowTable", "forward_return_flows","ACTION", "ACTION_NAMES", "RESULT_DTYPE", "STATUS", "STATUS_NAMES", "NetIf", "HaloError", "ArpTable", "NatTable",
            "Switch", "EGRESS_PORT_DTYPE", "EgressResult", "egress_arp", "egress_host", "egress_masks", "egress_switch",
-           "RespondResult", "build_replies", "respond", "respond_host", "tcp_port_map"]
+           "RespondResult", "build_replies", "respond", "respond_host", "tcp_port_map",
+           "DeliverResult", "deliver", "deliver_host", "port_map"]

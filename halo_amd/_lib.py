@@ -166,6 +166,19 @@ assert RESPOND_SRC_DTYPE.itemsize == 8
 RESPOND_KIND_NAMES = ("ECHO", "TTL", "TCP_SYN", "TCP_SYNACK")
 RESPOND_KIND = {name: code for code, name in enumerate(RESPOND_KIND_NAMES)}
 RESPOND_KIND_COUNT = len(RESPOND_KIND_NAMES)
+# local delivery: halo_deliver_hdr_t (24 bytes), halo_deliver_summary_t (40), halo_deliver_index_t (8), HALO_DELIVER_*
+DELIVER_HDR_DTYPE = np.dtype([("frame", "<u4"), ("kind", "u1"), ("tcp_flags", "u1"), ("payload_len", "<u2"),
+                              ("remote_ip", "<u4"), ("remote_port", "<u2"), ("local_port", "<u2"), ("seq", "<u4"),
+                              ("ack", "<u4")])
+DELIVER_SUMMARY_DTYPE = np.dtype([("records", "<u4"), ("records_written", "<u4"), ("bytes", "<u8"),
+                                  ("bytes_written", "<u8"), ("kind_counts", "<u4", (3,)), ("skipped", "<u4")])
+DELIVER_INDEX_DTYPE = np.dtype([("frame", "<u4"), ("offset", "<u4")])
+assert (DELIVER_HDR_DTYPE.itemsize, DELIVER_SUMMARY_DTYPE.itemsize, DELIVER_INDEX_DTYPE.itemsize) == (24, 40, 8)
+DELIVER_KIND_NAMES = ("UDP", "TCP", "DHCP")
+DELIVER_KIND = {name: code for code, name in enumerate(DELIVER_KIND_NAMES)}
+DELIVER_KIND_COUNT = len(DELIVER_KIND_NAMES)
+HALO_DELIVER_DHCP = 0x2  # also the bit of halo_deliver_config_t.flags that enables the kind
+DELIVER_NOT_WRITTEN = 0xFFFFFFFF  # an index entry's offset beyond the written prefix
 # halo_rx_ring_scan_t (24 bytes) and HALO_RING_STOP_* / HALO_RING_REGISTER
 RING_SCAN_DTYPE = np.dtype([("n_frames", "<u4"), ("stop", "<u4"), ("end_bytes", "<u8"), ("max_len", "<u4"),
                             ("pad", "<u4")])
@@ -310,6 +323,15 @@ class EgressConfig(ctypes.Structure):
 
 
 assert ctypes.sizeof(EgressConfig) == 24
+
+
+class DeliverConfig(ctypes.Structure):
+    """halo_deliver_config_t."""
+
+    _fields_ = [("flags", ctypes.c_uint32), ("index_cap", ctypes.c_uint32), ("region_bytes", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(DeliverConfig) == 16
 
 
 class BatchDesc(ctypes.Structure):
@@ -516,6 +538,12 @@ _PROTOS = {
     "halo_tx_respond_host": (ctypes.c_int, [
         _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(NetIf), _u8p, _u8p, _u8p, _u8p, _u8p, _u8p,
         _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    "halo_rx_deliver_workspace": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "halo_rx_deliver_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.POINTER(NetIf), _u8p, _u8p, _u8p, _u8p, _u8p,
+        _u8p, ctypes.c_uint64, ctypes.c_void_p]),
+    "halo_rx_deliver_host": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.POINTER(NetIf), _u8p, _u8p, _u8p, _u8p, _u8p]),
     "halo_synth_layout": (ctypes.c_int, [
         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint64)]),

@@ -1609,6 +1609,105 @@ HALO_API int halo_tx_respond_host(const uint32_t* offsets_dw, const uint16_t* le
                                   halo_tx_build_desc_t* desc, halo_respond_src_t* src, uint32_t* dst_ip, uint32_t cap,
                                   uint32_t* count, uint32_t* kind_counts, uint8_t* actions);
 
+/* ---- local delivery: service payload streams from a device-resident batch --------------------
+ * RxIpv4's fourth outcome (engine/ipv4_engine.go:18-47): RxUdp / RxTcp hand a payload to the
+ * handler registered for its destination port, and a broadcast UDP datagram to a DHCP port goes to
+ * RxDhcp. For a parsed batch that lies in HBM: from the frames, their offsets_dw / lens and their
+ * full records to ONE stream of delivery records in ascending frame index — the order in which the
+ * reference calls the handlers, across all services — so that a host downloads the served payloads
+ * and 24 bytes of header each, not the batch and its records. Per frame i, with a =
+ * halo_rx_dispatch's action of record i:
+ *   UDP   a == LOCAL_UDP and bit dport of d_udp_ports set (UdpServiceMap): handleFunc(UdpSession{
+ *         src, sport}, udpPayload)                                  engine/udp_engine.go:10-21
+ *   TCP   a == LOCAL_TCP and bit dport of d_tcp_ports set (TcpServiceMap): handleFunc(TcpSession{src,
+ *         sport}, tcpPayload, seqNum, ackNum, flags) for EVERY such segment, handshake segments and
+ *         empty payloads included (the handshake answers themselves are the responders')
+ *                                                                   engine/tcp_engine.go:10-26
+ *   DHCP  a == BCAST_UDP, dport == 67 or 68 (DhcpServerPort / DhcpClientPort) and HALO_DELIVER_DHCP
+ *         in cfg->flags: RxDhcp(udpPayload, udpSrcPort, udpDstPort, ipv4SrcAddr). The DHCP engine
+ *         stays on the host.                                        engine/udp_engine.go:35-44
+ * d_udp_ports / d_tcp_ports are 65,536 bits as 2,048 u32, bit p & 31 of word p >> 5, as
+ * halo_tx_respond_device takes them; NULL = no service of that protocol. With HALO_RX_L3_START in
+ * cfg->flags the records are LoChan packets (engine/engine.go:353-381): the action is
+ * halo_rx_dispatch_loopback's, payload_off is in packet coordinates and the DHCP row cannot occur.
+ * A selected frame whose record says payload_off + payload_len > lens[i] (a record that is not the
+ * frame's) is delivered nowhere and counted in `skipped`: no record makes the call read outside
+ * the frame it names.
+ * A RECORD is halo_deliver_hdr_t (24 B, little-endian), the payload_len payload bytes (the record's
+ * payload_off / payload_len slice of the frame: UDP pkt[8:], TCP pkt[headerLen:] with the
+ * data-offset nibble taken as bytes, protocol/tcp.go:49,68, so a payload starts at any of the four
+ * byte alignments), then zeros up to the next 4-byte boundary. Record size = 24 + ((payload_len +
+ * 3) & ~3); every record starts 4-byte aligned.
+ * REGION OVERFLOW (the egress rule): records are written while they fit wholly in region_bytes;
+ *   the first that does not fit ends the written prefix. `records` and `bytes` remain the totals.
+ * INDEX (optional): d_index[k] = {frame, offset} for k < min(records, index_cap); offset = the
+ *   record's byte offset in d_out, or 0xFFFFFFFF beyond the written prefix (and, for the host call
+ *   with a region above 4 GiB, for an offset that does not fit).
+ * READS: no byte of a frame that is not delivered; nothing outside the 4-byte words that hold a
+ *   delivered frame's bytes — only those that hold payload bytes are loaded, and the bytes of
+ *   those words outside the payload (headers, a neighbour's, a gap's) never reach the output. A
+ *   service-map word is read only for a LOCAL_UDP / LOCAL_TCP frame. The batch is never written.
+ * WRITES: exactly [0, bytes_written) of d_out, the summary (SET) and the index entries above;
+ *   nothing else.
+ * The device call is asynchronous on `stream` with no host round trip: three launches (per-tile
+ * counts, a scan over tiles that writes the summary, the scatter). n == 0 is OK and zeroes the
+ * summary. Every argument is checked before any device call. HALO_E_INVAL: a null cfg /
+ * netif / d_summary, a null array with n > 0, flags other than HALO_RX_L3_START |
+ * HALO_DELIVER_DHCP, region_bytes not a multiple of 16 or above 2^32 - 16, d_out null with
+ * region_bytes > 0, d_index null with index_cap > 0, a misaligned array (d_out, records: 16;
+ * summary, index, workspace: 8; bytes, maps, offsets: 4; lens: 2), workspace_bytes <
+ * halo_rx_deliver_workspace(n). HALO_E_NODEV / _ARCH as elsewhere.
+ * Not covered: a stream per service (the order the reference shows is the batch's; local_port and
+ * kind let a host split it); the DHCP engine. */
+#define HALO_DELIVER_UDP 0u
+#define HALO_DELIVER_TCP 1u
+#define HALO_DELIVER_DHCP 2u /* the kind, and the bit of halo_deliver_config_t.flags that enables it */
+#define HALO_DELIVER_KIND_COUNT 3u
+typedef struct halo_deliver_hdr {
+    uint32_t frame;       /* the frame's index in its batch         */
+    uint8_t kind;         /* HALO_DELIVER_*                         */
+    uint8_t tcp_flags;    /* l4_aux                                 */
+    uint16_t payload_len; /* bytes that follow, before the padding  */
+    uint32_t remote_ip;   /* src_ip                                 */
+    uint16_t remote_port; /* sport                                  */
+    uint16_t local_port;  /* dport                                  */
+    uint32_t seq;         /* l4_seq                                 */
+    uint32_t ack;         /* l4_ack                                 */
+} halo_deliver_hdr_t;     /* 24 B */
+typedef struct halo_deliver_config {
+    uint32_t flags;        /* HALO_RX_L3_START | HALO_DELIVER_DHCP                                   */
+    uint32_t index_cap;    /* entries in d_index (0 with d_index NULL)                               */
+    uint64_t region_bytes; /* bytes of d_out; a multiple of 16 and at most 2^32 - 16 for the device call */
+} halo_deliver_config_t;   /* 16 B */
+typedef struct halo_deliver_summary { /* SET by the call */
+    uint32_t records;         /* frames delivered, also beyond the region              */
+    uint32_t records_written; /* the prefix of them that fits the region wholly        */
+    uint64_t bytes;           /* sum of their record sizes                             */
+    uint64_t bytes_written;   /* <= region_bytes; a whole number of records            */
+    uint32_t kind_counts[HALO_DELIVER_KIND_COUNT]; /* of `records`, per kind            */
+    uint32_t skipped;         /* selected, but the record's payload overruns the frame */
+} halo_deliver_summary_t;     /* 40 B */
+typedef struct halo_deliver_index {
+    uint32_t frame;
+    uint32_t offset; /* of the record in d_out; 0xFFFFFFFF: not written */
+} halo_deliver_index_t; /* 8 B */
+/* Bytes of device workspace (8-byte aligned, no initialisation) for n frames. One workspace serves
+ * any number of calls issued on one stream. */
+HALO_API uint64_t halo_rx_deliver_workspace(uint32_t n);
+HALO_API int halo_rx_deliver_device(const halo_deliver_config_t* cfg, const uint8_t* d_bytes,
+                                    const uint32_t* d_offsets_dw, const uint16_t* d_lens,
+                                    const halo_rx_result_t* d_records, uint32_t n, const halo_rx_netif_t* netif,
+                                    const uint32_t* d_udp_ports, const uint32_t* d_tcp_ports, uint8_t* d_out,
+                                    halo_deliver_summary_t* d_summary, halo_deliver_index_t* d_index,
+                                    void* d_workspace, uint64_t workspace_bytes, halo_stream_t stream);
+/* The same outputs from the sequential loop over host memory; no HIP. The caller picks it by name
+ * for polls at the reference's cadence; it is never a fallback. Arrays need no alignment and
+ * region_bytes may be any value here. */
+HALO_API int halo_rx_deliver_host(const halo_deliver_config_t* cfg, const uint8_t* bytes, const uint32_t* offsets_dw,
+                                  const uint16_t* lens, const halo_rx_result_t* records, uint32_t n,
+                                  const halo_rx_netif_t* netif, const uint32_t* udp_ports, const uint32_t* tcp_ports,
+                                  uint8_t* out, halo_deliver_summary_t* summary, halo_deliver_index_t* index);
+
 /* ---- synthetic traffic (bench + tests; SURVEY.md §8d generator) ----------------------
  * Every field of frame i is a pure function of (seed, i), so any shard of the global
  * stream [first_index, first_index + n) is generated independently.
