@@ -22,7 +22,7 @@ BENCH_OUT = os.path.join(ROOT, "tools", "libhalo_bench.so")
 CPU_SRC = os.path.join(CSRC, "rx_cpu.cc")
 CPU_OUT = os.path.join(ROOT, "halo_amd", "lib", "libhalo_rx_cpu.so")
 HEADERS = ["halo_common.h", "halo_limits.h", "host_logic.h", "device_util.h", "flow_key.h", "nat_table.h", "switch_table.h", "arp_table.h", "tx_egress.h",
-           "tx_respond.h", "tx_ring.h", "rx_deliver.h", "pmflow_table.h", "rx_dispatch.h", "route_view.h", "tile_scan.h", "device_table.h", os.path.join("..", "..", "include", "halo_rx.h")]
+           "tx_respond.h", "tx_ring.h", "rx_deliver.h", "pmflow_table.h", "rx_dispatch.h", "route_view.h", "tile_scan.h", "stream_scan.h", "host_layout.h", "device_table.h", os.path.join("..", "..", "include", "halo_rx.h")]
 
 
 def _hipcc() -> str:

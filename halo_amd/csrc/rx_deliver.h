@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/halo_rx.h"
+#include "host_layout.h"
 #include "rx_dispatch.h"
 
 namespace halo {
@@ -91,11 +92,7 @@ HALO_DELIVER_FN uint32_t tail_mask(uint32_t plen, uint32_t j) {
 // scan turns into the rank base, then a u32 byte count (a tile's record bytes fit: 256 * 65,560),
 // then the tile's UDP, TCP and skipped counts in one u32 (each at most kTile = 256: nine bits); the
 // DHCP count is the rest of the records. 20 bytes per tile, rounded up to the 8-byte alignment.
-HALO_DELIVER_FN uint64_t tiles_of(uint32_t n) {
-    const uint64_t t = ((uint64_t)n + kTile - 1) / kTile;
-    return t ? t : 1;
-}
-HALO_DELIVER_FN uint64_t workspace_bytes(uint32_t n) { return (20ull * tiles_of(n) + 7) & ~7ull; }
+HALO_DELIVER_FN uint64_t workspace_bytes(uint32_t n) { return (20ull * tiles_of(n, kTile) + 7) & ~7ull; }
 static_assert(kTile <= 0x1FFu, "a tile's count fits nine bits");
 HALO_DELIVER_FN uint32_t pack_kinds(uint32_t udp, uint32_t tcp, uint32_t skipped) { return udp | tcp << 9 | skipped << 18; }
 HALO_DELIVER_FN uint32_t packed_udp(uint32_t w) { return w & 0x1FFu; }

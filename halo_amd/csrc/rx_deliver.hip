@@ -11,16 +11,14 @@
 //            the tile's record count, record bytes and packed UDP / TCP / skipped counts go to the
 //            workspace. (One atomic per workgroup and counter into the summary was measured
 //            first: the atomics of 4,096 workgroups on one address took 40 of the kernel's 52 us.)
-//   scan     one workgroup: exclusive scan over the tiles, kScanPass tiles per pass, u32 rank bases
-//            and u64 byte bases together, and the sums of the packed counts; writes the whole
-//            summary, so nothing has to be cleared first. The written prefix is the totals when
-//            they fit the region; otherwise the tile the cut falls in has base <= region < base +
-//            bytes, its lane writes the prefix of whole tiles before it, and the scatter adds that
-//            one tile's own part.
+//   scan     one workgroup: the streams' scan (stream_scan.h) over the tiles, u32 rank bases and
+//            u64 byte bases together, and the sums of the packed counts; writes the whole summary,
+//            so nothing has to be cleared first. With a cut, the written prefix is that of the
+//            whole tiles before it, and the scatter adds the cut tile's own part.
 //   scatter  a tile without deliveries, or wholly beyond the region and the index, ends at once.
 //            Else the decision again, ranks from tile_votes / tile_rank, byte offsets from a wave
-//            scan of record sizes plus the wave totals in LDS. The owning lane writes the header (a
-//            16-byte and an 8-byte store) and the index entry and leaves a descriptor in LDS; the
+//            scan of record sizes plus the wave totals in LDS. The owning lane writes the header
+//            (a 16-byte and an 8-byte store) and the index entry and leaves a descriptor in LDS; the
 //            workgroup then copies the payloads, a group of lanes per record walking the record's
 //            ALIGNED DESTINATION dwords: each is funnelled out of the two source dwords it spans
 //            with v_alignbyte_b32 at shift payload_off & 3 — the upper one is not loaded when no
@@ -31,7 +29,7 @@
 
 #include "halo_common.h"
 #include "rx_deliver.h"
-#include "tile_scan.h"
+#include "stream_scan.h"
 
 namespace halo {
 namespace {
@@ -93,8 +91,7 @@ __global__ void __launch_bounds__(kTile) deliver_count_kernel(const DeliverParam
     const uint32_t kind = frame_kind(q, blockIdx.x * kTile + threadIdx.x, &r, &skip);
     const uint64_t sel = __ballot(kind != kNone), skips = __ballot(skip);
     if (sel) {  // wave-uniform
-        uint32_t bytes = kind != kNone ? deliver::record_size(deliver::payload_len(r)) : 0u;
-        for (uint32_t d = 32; d; d >>= 1) bytes += __shfl_xor(bytes, d, 64);
+        const uint32_t bytes = wave_sum(kind != kNone ? deliver::record_size(deliver::payload_len(r)) : 0u);
         const uint32_t udp = (uint32_t)__popcll(__ballot(kind == HALO_DELIVER_UDP));
         const uint32_t tcp = (uint32_t)__popcll(__ballot(kind == HALO_DELIVER_TCP));
         if ((threadIdx.x & 63u) == 0) {
@@ -113,71 +110,31 @@ __global__ void __launch_bounds__(kTile) deliver_count_kernel(const DeliverParam
     }
 }
 
-// One workgroup, tx_egress.hip's scan for one stream: one barrier per pass, the wave totals
-// double-buffered and the carry in registers.
+// One workgroup: stream_scan.h's scan over the tiles, the packed per-kind counts summed on the way.
 __global__ void __launch_bounds__(256) deliver_scan_kernel(const DeliverParams q) {
-    __shared__ uint32_t s_wave_c[2][4], s_kind[4];
-    __shared__ unsigned long long s_wave_b[2][4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n_tiles = q.n_tiles;
-    halo_deliver_summary_t* o = q.summary;
-    uint32_t base_c = 0, par = 0, udp = 0, tcp = 0, skipped = 0;  // the three: this lane's tiles only, until the end
-    unsigned long long base_b = 0;
-    for (uint32_t t0 = 0; t0 < n_tiles; t0 += kScanPass, par ^= 1) {
-        const uint32_t t = t0 + 4 * threadIdx.x;
-        uint32_t c[4], b[4], csum = 0;
-        unsigned long long bsum = 0;
-        for (uint32_t k = 0; k < 4; ++k) {
-            c[k] = t + k < n_tiles ? q.rank_base[t + k] : 0u;
-            b[k] = t + k < n_tiles ? q.tile_bytes[t + k] : 0u;
-            const uint32_t kinds = t + k < n_tiles ? q.tile_kinds[t + k] : 0u;
-            csum += c[k];
-            bsum += b[k];
+    __shared__ StreamScanLds s_scan;
+    __shared__ uint32_t s_kind[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    StreamSummary* o = reinterpret_cast<StreamSummary*>(q.summary);
+    uint32_t udp = 0, tcp = 0, skipped = 0;  // this lane's tiles only, until the end
+    const StreamTotals all =
+        scan_stream_tiles(s_scan, q.rank_base, q.tile_bytes, q.byte_base, q.n_tiles, q.region, o, [&](uint32_t t, bool in) {
+            const uint32_t kinds = in ? q.tile_kinds[t] : 0u;
             udp += deliver::packed_udp(kinds), tcp += deliver::packed_tcp(kinds), skipped += deliver::packed_skipped(kinds);
-        }
-        uint32_t cinc = csum;
-        unsigned long long binc = bsum;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t yc = __shfl_up(cinc, d, 64);
-            const unsigned long long yb = __shfl_up(binc, d, 64);
-            if (lane >= d) cinc += yc, binc += yb;
-        }
-        if (lane == 63) s_wave_c[par][wave] = cinc, s_wave_b[par][wave] = binc;
-        __syncthreads();
-        uint32_t run_c = base_c + cinc - csum;
-        unsigned long long run_b = base_b + binc - bsum;
-        for (uint32_t w = 0; w < 4; ++w) {
-            if (w < wave) run_c += s_wave_c[par][w], run_b += s_wave_b[par][w];
-            base_c += s_wave_c[par][w];
-            base_b += s_wave_b[par][w];
-        }
-        for (uint32_t k = 0; k < 4; ++k) {
-            if (t + k < n_tiles) {
-                q.rank_base[t + k] = run_c;
-                q.byte_base[t + k] = run_b;
-                if (run_b <= q.region && run_b + b[k] > q.region) {  // the cut falls in this tile
-                    o->records_written = run_c;
-                    o->bytes_written = run_b;
-                }
-            }
-            run_c += c[k];
-            run_b += b[k];
-        }
-    }
+        });
     // the per-kind totals: order-free sums, one reduction after the last pass
-    for (uint32_t d = 32; d; d >>= 1) udp += __shfl_xor(udp, d, 64), tcp += __shfl_xor(tcp, d, 64), skipped += __shfl_xor(skipped, d, 64);
-    __syncthreads();  // the last pass's readers of s_wave_c are done
-    if (lane == 0) s_wave_c[0][wave] = udp, s_wave_c[1][wave] = tcp, s_kind[wave] = skipped;
+    udp = wave_sum(udp), tcp = wave_sum(tcp), skipped = wave_sum(skipped);
+    __syncthreads();  // the last pass's readers of s_scan are done: its count slots serve again
+    if (lane == 0) s_scan.c[0][wave] = udp, s_scan.c[1][wave] = tcp, s_kind[wave] = skipped;
     __syncthreads();
     if (threadIdx.x == 0) {
-        udp = s_wave_c[0][0] + s_wave_c[0][1] + s_wave_c[0][2] + s_wave_c[0][3];
-        tcp = s_wave_c[1][0] + s_wave_c[1][1] + s_wave_c[1][2] + s_wave_c[1][3];
-        o->records = base_c;
-        o->bytes = base_b;
-        if (base_b <= q.region) o->records_written = base_c, o->bytes_written = base_b;  // no cut
-        o->kind_counts[HALO_DELIVER_UDP] = udp;
-        o->kind_counts[HALO_DELIVER_TCP] = tcp;
-        o->kind_counts[HALO_DELIVER_DHCP] = base_c - udp - tcp;
-        o->skipped = s_kind[0] + s_kind[1] + s_kind[2] + s_kind[3];
+        udp = s_scan.c[0][0] + s_scan.c[0][1] + s_scan.c[0][2] + s_scan.c[0][3];
+        tcp = s_scan.c[1][0] + s_scan.c[1][1] + s_scan.c[1][2] + s_scan.c[1][3];
+        write_stream_totals(o, all, q.region);
+        q.summary->kind_counts[HALO_DELIVER_UDP] = udp;
+        q.summary->kind_counts[HALO_DELIVER_TCP] = tcp;
+        q.summary->kind_counts[HALO_DELIVER_DHCP] = all.c - udp - tcp;
+        q.summary->skipped = s_kind[0] + s_kind[1] + s_kind[2] + s_kind[3];
     }
 }
 
@@ -215,11 +172,7 @@ __global__ void __launch_bounds__(kTile) deliver_scatter_kernel(const DeliverPar
     const uint32_t kind = frame_kind(q, i, &r, &skip);
     const bool sel = kind != kNone;
     const uint32_t size = sel ? deliver::record_size(deliver::payload_len(r)) : 0u;
-    uint32_t inc = size;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += y;
-    }
+    const uint32_t inc = wave_inclusive(size, lane);
     if (lane == 63) s_wbytes[wave] = inc;
     const uint64_t votes = tile_votes<kTile>(sel);
     const uint32_t rank = tile_rank<kTile>(votes, 0u);
@@ -268,7 +221,7 @@ int ops_run(const halo_deliver_config_t* cfg, const uint8_t* d_bytes, const uint
     q.bytes = d_bytes, q.offsets_dw = d_offsets_dw, q.lens = d_lens, q.recs = d_records;
     q.udp_ports = d_udp_ports, q.tcp_ports = d_tcp_ports;
     q.region = cfg->region_bytes;
-    q.n = n, q.n_tiles = (uint32_t)deliver::tiles_of(n), q.flags = cfg->flags, q.nat_enable = netif->nat_enable ? 1u : 0u;
+    q.n = n, q.n_tiles = (uint32_t)tiles_of(n, kTile), q.flags = cfg->flags, q.nat_enable = netif->nat_enable ? 1u : 0u;
     q.index_cap = d_index ? cfg->index_cap : 0u;
     q.out = d_out, q.summary = d_summary, q.index = reinterpret_cast<uint2*>(d_index);
     q.byte_base = static_cast<uint64_t*>(d_workspace);

@@ -11,8 +11,6 @@ namespace halo {
 namespace deliver {
 namespace {
 
-inline bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) & (a - 1); }
-
 // What both entry points ask
 int check(const halo_deliver_config_t* cfg, const uint8_t* bytes, const uint32_t* offsets_dw, const uint16_t* lens,
           const halo_rx_result_t* records, uint32_t n, const halo_rx_netif_t* netif, const uint8_t* out,
@@ -25,16 +23,11 @@ int check(const halo_deliver_config_t* cfg, const uint8_t* bytes, const uint32_t
     return HALO_OK;
 }
 
-inline uint32_t load_u32(const void* p) {
-    uint32_t w;
-    memcpy(&w, p, 4);
-    return w;
-}
-
 }  // namespace
 }  // namespace deliver
 }  // namespace halo
 
+using namespace halo;  // host_layout.h
 using namespace halo::deliver;
 
 extern "C" HALO_API uint64_t halo_rx_deliver_workspace(uint32_t n) { return workspace_bytes(n); }

@@ -1,8 +1,8 @@
 // tile_scan.h — the workgroup-level steps of the count / scan / scatter kernels (arp_fwd.hip's
 // gather, pmflow_fwd.hip's listing, tx_respond.hip, switch_fwd.hip's probe / scan / admit): a
 // tile's count of selected lanes, the one-workgroup exclusive scan over the tile counts, and a
-// lane's rank among the selected lanes of its tile. tx_egress.hip takes lanes_below and kScanPass
-// only: its scan is a fused one of counts and bytes. gfx950 (CDNA4, wave64) only.
+// lane's rank among the selected lanes of its tile; and the wave's inclusive prefix sum. The stream
+// stages scan counts and bytes together: stream_scan.h, on top of this. gfx950 (CDNA4, wave64) only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,6 +13,16 @@ namespace {
 // the number of set ballot bits below the calling lane
 __device__ __forceinline__ uint32_t lanes_below(uint64_t ballot) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
+
+// x (u32 or u64) summed over the caller's lane (threadIdx.x & 63) and the lanes below it in the wave
+template <typename T>
+__device__ __forceinline__ T wave_inclusive(T x, uint32_t lane) {
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const T y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    return x;
 }
 
 constexpr uint32_t kScanPass = 1024;  // tiles per pass of a scan: four consecutive tiles per lane
@@ -48,11 +58,7 @@ __device__ __forceinline__ uint32_t scan_tiles(uint32_t* tiles, uint32_t n_tiles
             x[k] = t + k < n_tiles ? tiles[t + k] : 0u;
             sum += x[k];
         }
-        uint32_t inc = sum;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += y;
-        }
+        const uint32_t inc = wave_inclusive(sum, lane);
         if (lane == 63) s_wave[wave] = inc;
         __syncthreads();
         uint32_t before = s_base;

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/halo_rx.h"
+#include "host_layout.h"
 
 namespace halo {
 namespace egress {
@@ -38,13 +39,6 @@ HALO_EGRESS_FN uint64_t mask_of_switch(uint32_t w, uint64_t flood_mask) {
     const uint32_t v = w & 0xFFu, out = (w >> 8) & 0xFFu;
     if (v == HALO_SW_V_FLOOD) return flood_mask;
     return v == HALO_SW_V_UNICAST && out < 64u ? 1ull << out : 0ull;
-}
-
-// Workspace of a device call: per port and tile a u64 byte base, then a u32 record count that the
-// scan turns into the rank base, then a u32 byte count. Column-major: port p's tiles are contiguous.
-HALO_EGRESS_FN uint64_t tiles_of(uint32_t n) {
-    const uint64_t t = ((uint64_t)n + kTile - 1) / kTile;
-    return t ? t : 1;
 }
 
 // The device side (tx_egress.hip); tx_egress_host.cc reaches it only through this, after it has

@@ -7,24 +7,21 @@
 //   count    one workgroup per tile of kTile frames (grid-stride over tiles): per port the tile's
 //            record count and record bytes through LDS atomics (totals are order-free): one pair
 //            per wave and port when a wave's frames all go the same way, else one per frame.
-//   scan     one workgroup per port: exclusive scan over the port's tiles, kScanPass tiles per pass,
-//            u32 rank bases and u64 byte bases; writes the port's summary. The written prefix is
-//            the totals when they fit the region; otherwise the tile the cut falls in has
-//            base <= region < base + bytes, its lane writes the prefix of whole tiles before it,
-//            and the scatter adds that one tile's own part (one workgroup per port: no atomics).
+//   scan     one workgroup per port: the streams' scan (stream_scan.h) over the port's tiles, u32
+//            rank bases and u64 byte bases; writes the port's summary. With a cut, the written
+//            prefix is that of the whole tiles before it, and the scatter adds the cut tile's own
+//            part (one workgroup per port: no atomics).
 //   scatter  recomputes the masks; then per port that any frame of the tile goes to (a loop that is
 //            uniform over the workgroup): ballot + mbcnt ranks and a wave scan of record sizes, wave
 //            totals through LDS, the tile's bases added; every record that fits leaves a descriptor
-//            in LDS and the workgroup copies them, kLanesPerRec lanes per short record (a wave per
-//            long one), one record's consecutive dwords per group, so that a group stores 64
-//            contiguous bytes and neighbouring groups neighbouring records. Source and destination
-//            are 4-byte aligned by construction. The last source dword is masked to len, the rest
-//            of the record is zeros.
+//            in LDS and the workgroup copies them, kLanesPerRec lanes
+//            per short record (a wave per long one). Source and destination are 4-byte aligned by
+//            construction. The last source dword is masked to len, the rest of the record is zeros.
 // The three front ends instantiate one body that differs only in how a frame's port mask is decoded.
 #include <hip/hip_runtime.h>
 
 #include "halo_common.h"
-#include "tile_scan.h"
+#include "stream_scan.h"
 #include "tx_egress.h"
 
 namespace halo {
@@ -92,8 +89,7 @@ __global__ void __launch_bounds__(kTile) egress_count_kernel(const EgressParams 
         if (act) {
             const unsigned long long lead = __shfl((unsigned long long)m, (int)__builtin_ctzll(act), 64);
             if (__ballot(m != 0 && m != lead) == 0) {
-                uint32_t bytes = m ? rec : 0u;
-                for (uint32_t d = 32; d; d >>= 1) bytes += __shfl_xor(bytes, d, 64);
+                const uint32_t bytes = wave_sum(m ? rec : 0u);
                 if ((threadIdx.x & 63u) == 0) {
                     for (uint64_t rest = lead; rest; rest &= rest - 1) {
                         const uint32_t p = (uint32_t)__builtin_ctzll(rest);
@@ -119,64 +115,14 @@ __global__ void __launch_bounds__(kTile) egress_count_kernel(const EgressParams 
     if ((threadIdx.x & 63u) == 0 && skips && q.skipped) atomicAdd(q.skipped, skips);
 }
 
-// One workgroup per port. One barrier per pass: the wave totals are double-buffered and the carry
-// lives in registers. The port's written prefix needs no reduction: the tile the cut falls in is
-// the one with base <= region < base + bytes, and its lane writes the prefix of whole tiles before
-// it (the scatter adds that tile's own part); without a cut the totals are the prefix.
+// One workgroup per port: stream_scan.h's scan over the port's tiles, then the port's totals.
 __global__ void __launch_bounds__(256) egress_scan_kernel(const EgressParams q) {
-    __shared__ uint32_t s_wave_c[2][4];
-    __shared__ unsigned long long s_wave_b[2][4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, n_tiles = q.n_tiles;
-    uint32_t* cnt = q.rank_base + (uint64_t)blockIdx.x * n_tiles;
-    const uint32_t* tb = q.tile_bytes + (uint64_t)blockIdx.x * n_tiles;
-    uint64_t* bb = q.byte_base + (uint64_t)blockIdx.x * n_tiles;
-    halo_egress_port_t* o = q.ports + blockIdx.x;
-    uint32_t base_c = 0, par = 0;
-    unsigned long long base_b = 0;
-    for (uint32_t t0 = 0; t0 < n_tiles; t0 += kScanPass, par ^= 1) {
-        const uint32_t t = t0 + 4 * threadIdx.x;
-        uint32_t c[4], b[4], csum = 0;
-        unsigned long long bsum = 0;
-        for (uint32_t k = 0; k < 4; ++k) {
-            c[k] = t + k < n_tiles ? cnt[t + k] : 0u;
-            b[k] = t + k < n_tiles ? tb[t + k] : 0u;
-            csum += c[k];
-            bsum += b[k];
-        }
-        uint32_t cinc = csum;
-        unsigned long long binc = bsum;
-        for (uint32_t d = 1; d < 64; d <<= 1) {
-            const uint32_t yc = __shfl_up(cinc, d, 64);
-            const unsigned long long yb = __shfl_up(binc, d, 64);
-            if (lane >= d) cinc += yc, binc += yb;
-        }
-        if (lane == 63) s_wave_c[par][wave] = cinc, s_wave_b[par][wave] = binc;
-        __syncthreads();
-        uint32_t run_c = base_c + cinc - csum;
-        unsigned long long run_b = base_b + binc - bsum;
-        for (uint32_t w = 0; w < 4; ++w) {
-            if (w < wave) run_c += s_wave_c[par][w], run_b += s_wave_b[par][w];
-            base_c += s_wave_c[par][w];
-            base_b += s_wave_b[par][w];
-        }
-        for (uint32_t k = 0; k < 4; ++k) {
-            if (t + k < n_tiles) {
-                cnt[t + k] = run_c;
-                bb[t + k] = run_b;
-                if (run_b <= q.region && run_b + b[k] > q.region) {  // the cut falls in this tile
-                    o->frames_written = run_c;
-                    o->bytes_written = run_b;
-                }
-            }
-            run_c += c[k];
-            run_b += b[k];
-        }
-    }
-    if (threadIdx.x == 0) {
-        o->frames = base_c;
-        o->bytes = base_b;
-        if (base_b <= q.region) o->frames_written = base_c, o->bytes_written = base_b;  // no cut
-    }
+    __shared__ StreamScanLds s_scan;
+    const uint64_t first = (uint64_t)blockIdx.x * q.n_tiles;
+    StreamSummary* o = reinterpret_cast<StreamSummary*>(q.ports + blockIdx.x);
+    const StreamTotals all = scan_stream_tiles(s_scan, q.rank_base + first, q.tile_bytes + first, q.byte_base + first, q.n_tiles,
+                                             q.region, o, [](uint32_t, bool) {});
+    if (threadIdx.x == 0) write_stream_totals(o, all, q.region);
 }
 
 // Dword j of the record of a frame of len bytes at src: the length word, the frame's dwords with
@@ -235,11 +181,7 @@ __global__ void __launch_bounds__(kTile) egress_scatter_kernel(const EgressParam
             const bool sel = (m >> p) & 1;
             const uint64_t b = __ballot(sel);
             const uint32_t size = sel ? rec : 0u;
-            uint32_t inc = size;
-            for (uint32_t d = 1; d < 64; d <<= 1) {
-                const uint32_t y = __shfl_up(inc, d, 64);
-                if (lane >= d) inc += y;
-            }
+            const uint32_t inc = wave_inclusive(size, lane);
             if (lane == 63) s_wcnt[par][wave] = (uint32_t)__popcll(b), s_wbytes[par][wave] = inc;
             if (threadIdx.x == 0) s_nfit[par] = 0, s_fit_end[par] = 0;
             __syncthreads();
@@ -300,7 +242,7 @@ int ops_run(const halo_egress_config_t* cfg, uint32_t kind, const uint8_t* d_byt
     EgressParams q{};
     q.bytes = d_bytes, q.offsets_dw = d_offsets_dw, q.lens = d_lens, q.sel = d_selectors;
     q.flood = flood_mask, q.valid = egress::port_bits(cfg->n_ports), q.region = cfg->region_bytes;
-    q.n = n, q.n_tiles = (uint32_t)egress::tiles_of(n), q.n_ports = cfg->n_ports, q.flags = cfg->flags;
+    q.n = n, q.n_tiles = (uint32_t)tiles_of(n, kTile), q.n_ports = cfg->n_ports, q.flags = cfg->flags;
     q.index_cap = d_index ? cfg->index_cap : 0u;
     q.out = d_out, q.ports = d_ports, q.index = d_index, q.skipped = d_skipped;
     const uint64_t cells = (uint64_t)q.n_tiles * q.n_ports;

@@ -11,8 +11,6 @@ namespace halo {
 namespace egress {
 namespace {
 
-inline bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) & (a - 1); }
-
 // What all four entry points ask of cfg and the outputs
 int check_common(const halo_egress_config_t* cfg, const void* out, uintptr_t out_align, const halo_egress_port_t* ports,
                  const uint32_t* index, const uint32_t* skipped) {
@@ -50,21 +48,18 @@ int device_call(const halo_egress_config_t* cfg, uint32_t kind, uintptr_t select
                : HALO_E_NODEV;
 }
 
-inline uint32_t load_u32(const void* p) {
-    uint32_t w;
-    memcpy(&w, p, 4);
-    return w;
-}
-
 }  // namespace
 }  // namespace egress
 }  // namespace halo
 
+using namespace halo;  // host_layout.h
 using namespace halo::egress;
 
+// Workspace of a device call: per port and tile a u64 byte base, then a u32 record count that the
+// scan turns into the rank base, then a u32 byte count. Column-major: port p's tiles are contiguous.
 extern "C" HALO_API uint64_t halo_tx_egress_workspace(uint32_t n, uint32_t n_ports) {
     if (n_ports < 1 || n_ports > HALO_EGRESS_MAX_PORTS) return 0;
-    return 16ull * tiles_of(n) * n_ports;
+    return 16ull * tiles_of(n, kTile) * n_ports;
 }
 
 extern "C" HALO_API int halo_tx_egress_masks_device(const halo_egress_config_t* cfg, const uint8_t* d_bytes,

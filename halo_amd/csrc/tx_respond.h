@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/halo_rx.h"
+#include "host_layout.h"
 #include "rx_dispatch.h"
 
 namespace halo {
@@ -86,11 +87,6 @@ HALO_RESPOND_FN Reply decide(const Rec& r, uint32_t len, uint32_t off_dw, uint32
         o.ack = r.l4_seq + 1u;
     }
     return o;
-}
-
-HALO_RESPOND_FN uint64_t tiles_of(uint32_t n) {
-    const uint64_t t = ((uint64_t)n + kTile - 1) / kTile;
-    return t ? t : 1;
 }
 
 // The device side (tx_respond.hip); tx_respond_host.cc reaches it only through this, after it

@@ -121,7 +121,7 @@ int ops_run(const uint32_t* d_offsets_dw, const uint16_t* d_lens, const halo_rx_
     const Args a{d_records, d_nat_verdict, reinterpret_cast<const uint8_t*>(d_ops), d_fixup_result, d_tcp_ports,
                  n,         flags,         netif->ip,                               netif->nat_enable ? 1u : 0u};
     uint32_t* tiles = static_cast<uint32_t*>(d_workspace);
-    const uint32_t n_tiles = (uint32_t)respond::tiles_of(n);
+    const uint32_t n_tiles = (uint32_t)tiles_of(n, kTile);
     hipLaunchKernelGGL(respond_count_kernel, dim3(n_tiles), dim3(kTile), 0, st, a, tiles, d_actions, d_kind_counts);
     hipLaunchKernelGGL(respond_scan_kernel, dim3(1), dim3(256), 0, st, tiles, n_tiles, d_count);
     hipLaunchKernelGGL(respond_scatter_kernel, dim3(n_tiles), dim3(kTile), 0, st, a, d_offsets_dw, d_lens, tiles, d_desc,

@@ -11,8 +11,6 @@ namespace halo {
 namespace respond {
 namespace {
 
-inline bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) & (a - 1); }
-
 // What both entry points ask; `dev` adds the alignment the kernels' vector accesses need.
 int check(const uint32_t* offsets_dw, const uint16_t* lens, const halo_rx_result_t* records, uint32_t n, uint32_t flags,
           const halo_rx_netif_t* netif, const halo_tx_op_t* ops, const uint8_t* fixup_result,
@@ -27,19 +25,14 @@ int check(const uint32_t* offsets_dw, const uint16_t* lens, const halo_rx_result
     return HALO_OK;
 }
 
-inline uint32_t load_u32(const void* p) {
-    uint32_t w;
-    memcpy(&w, p, 4);
-    return w;
-}
-
 }  // namespace
 }  // namespace respond
 }  // namespace halo
 
+using namespace halo;  // host_layout.h
 using namespace halo::respond;
 
-extern "C" HALO_API uint64_t halo_tx_respond_workspace(uint32_t n) { return 4 * tiles_of(n); }  // one u32 per tile
+extern "C" HALO_API uint64_t halo_tx_respond_workspace(uint32_t n) { return 4 * tiles_of(n, kTile); }  // one u32 per tile
 
 extern "C" HALO_API int halo_tx_respond_device(const uint32_t* d_offsets_dw, const uint16_t* d_lens,
                                                const halo_rx_result_t* d_records, uint32_t n, uint32_t flags,

@@ -2,19 +2,11 @@
 // producer"): every argument check and the validation of the ring's header, answered before any
 // device is looked for. Checks only; no HIP: attach's registration and the kernels live in
 // tx_ring.hip behind txring::device_ops().
+#include "host_layout.h"
 #include "host_logic.h"
 #include "tx_ring.h"
 
-namespace halo {
-namespace txring {
-namespace {
-
-inline bool misaligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) & (a - 1); }
-
-}  // namespace
-}  // namespace txring
-}  // namespace halo
-
+using namespace halo;  // host_layout.h
 using namespace halo::txring;
 
 extern "C" HALO_API int halo_tx_ring_attach(int device, void* ring_mem, int64_t offset, uint32_t attach_flags,

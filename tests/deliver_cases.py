@@ -216,27 +216,50 @@ def read_constants() -> dict:
         hdr = fh.read()
     with open(os.path.join(CSRC, "tile_scan.h")) as fh:
         scan = fh.read()
-    # one workgroup per tile in both tile kernels: no grid cap, so no further edge; the scan's one
-    # loop advances by the shared kScanPass
+    with open(os.path.join(CSRC, "stream_scan.h")) as fh:
+        stream = fh.read()
+    # one workgroup per tile in both tile kernels: no grid cap, so no further edge; the scan kernel
+    # calls the streams' fused scan (stream_scan.h), whose one loop advances by the shared kScanPass
     assert len(re.findall(r"dim3\(q\.n_tiles\), dim3\(kTile\)", hip)) == 2 and "kMax" not in hip
-    assert _one(r"t0 < n_tiles; t0 \+= (\w+),", hip) == "kScanPass"
+    assert '#include "stream_scan.h"' in hip and "t0 +=" not in hip and "kScanPass =" not in hip + stream
+    _one(r"__global__ void __launch_bounds__\(256\) deliver_scan_kernel\([^)]*\) \{[^}]*?=\s*scan_stream_tiles\(", hip)
+    assert len(re.findall(r"scan_stream_tiles\(", hip)) == 1 and '#include "tile_scan.h"' in stream
+    assert _one(r"t0 < n_tiles; t0 \+= (\w+),", stream) == "kScanPass"
     return {"kTile": int(_one(r"constexpr uint32_t kTile = (\d+);", hdr)),
             "kScanPass": int(_one(r"constexpr uint32_t kScanPass = (\d+);", scan))}
 
 
-def uniform_batch(n: int, deliver_at):
+OVERRUN = 4  # uniform_batch's template whose record is made to overrun its frame
+
+
+def uniform_batch(n: int, deliver_at, tcp_at=(), dhcp_at=(), overrun_at=()):
     """n 64-byte frames back to back: template 0 (UDP to an unserved port) everywhere except
-    template 1 (UDP to a served port) at the indices `deliver_at`. Returns (templates, tid, data,
-    offsets_dw, lens)."""
-    t0, t1 = udp(54, bytes(range(22))), udp(53, bytes(range(100, 122)))
-    assert len(t0) == len(t1) == 64
+    template 1 (UDP to a served port) at the indices `deliver_at`, template 2 (TCP to a served
+    port) at `tcp_at`, template 3 (a DHCP broadcast) at `dhcp_at` and template 4 (UDP to a served
+    port; uniform_records makes its record overrun the frame) at `overrun_at`. Returns (templates,
+    tid, data, offsets_dw, lens)."""
+    templates = [udp(54, bytes(range(22))), udp(53, bytes(range(100, 122))), tcp(80, 0x18, bytes(range(50, 60)), seq=7, ack=11),
+                 udp(67, bytes(range(200, 222)), src=0, dst=BCAST, sport=68), udp(4000, bytes(range(150, 172)))]
+    assert {len(t) for t in templates} == {64}
     tid = np.zeros(n, np.int64)
-    tid[np.asarray(deliver_at, np.int64)] = 1
-    both = np.stack([np.frombuffer(t0, np.uint8), np.frombuffer(t1, np.uint8)])
-    data = both[tid].reshape(-1)
-    return [t0, t1], tid, data, (np.arange(n, dtype=np.int64) * 16).astype(np.uint32), np.full(n, 64, np.uint16)
+    for k, at in enumerate((deliver_at, tcp_at, dhcp_at, overrun_at), 1):
+        at = np.asarray(at, np.int64)
+        assert not tid[at].any(), "an index is given twice"
+        tid[at] = k
+    data = np.stack([np.frombuffer(t, np.uint8) for t in templates])[tid].reshape(-1)
+    return templates, tid, data, (np.arange(n, dtype=np.int64) * 16).astype(np.uint32), np.full(n, 64, np.uint16)
+
+
+def uniform_records(templates, tid, nif):
+    """The records of a uniform batch; those of template OVERRUN end one byte behind their frames,
+    as tests/test_gpu_deliver.py's overrun test makes them."""
+    recs = records(templates, nif)[tid]
+    bad = tid == OVERRUN
+    recs["payload_len"][bad] = 64 - recs["payload_off"][bad] + 1
+    return recs
 
 
 def uniform_want(templates, tid, nif, **kw) -> DM.Want:
-    per = [DM.delivery_of(t, nif, **kw) for t in templates]
-    return DM.Want([(int(i), per[tid[i]]) for i in np.flatnonzero(np.array([p is not None for p in per])[tid])])
+    per = [None if k == OVERRUN else DM.delivery_of(t, nif, **kw) for k, t in enumerate(templates)]
+    return DM.Want([(int(i), per[tid[i]]) for i in np.flatnonzero(np.array([p is not None for p in per])[tid])],
+                   skipped=int(np.count_nonzero(tid == OVERRUN)))

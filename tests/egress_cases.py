@@ -95,11 +95,16 @@ def read_constants() -> dict:
     blocks = 1
     for f in kmax.split("*"):
         blocks *= int(re.fullmatch(r"\s*(\d+)(?:ull|u)?\s*", f).group(1))
-    # egress_scan_kernel keeps its own fused loop and takes its pass from tile_scan.h
+    # egress_scan_kernel calls the streams' fused scan (stream_scan.h), whose one loop advances by
+    # tile_scan.h's pass; the file has no scan loop of its own
     with open(os.path.join(CSRC, "tile_scan.h")) as fh:
         tile = fh.read()
-    assert '#include "tile_scan.h"' in hip and "kScanPass =" not in hip
-    assert _one(r"t0 < n_tiles; t0 \+= (\w+),", hip) == "kScanPass"
+    with open(os.path.join(CSRC, "stream_scan.h")) as fh:
+        stream = fh.read()
+    assert '#include "stream_scan.h"' in hip and "t0 +=" not in hip and "kScanPass =" not in hip + stream
+    _one(r"__global__ void __launch_bounds__\(256\) egress_scan_kernel\([^)]*\) \{[^}]*?=\s*scan_stream_tiles\(", hip)
+    assert len(re.findall(r"scan_stream_tiles\(", hip)) == 1 and '#include "tile_scan.h"' in stream
+    assert _one(r"t0 < n_tiles; t0 \+= (\w+),", stream) == "kScanPass"
     return {"kTile": int(_one(r"constexpr uint32_t kTile = (\d+);", hdr)),
             "kScanPass": int(_one(r"constexpr uint32_t kScanPass = (\d+);", tile)),
             "egress_blocks": blocks}

@@ -162,11 +162,11 @@ def test_records_that_overrun_their_frames_are_skipped(dev):
     _same_as_host(got, data, offs, lens, recs_h, False)
 
 
-def _uniform(dev, n, deliver_at):
-    templates, tid, data, offs, lens = C.uniform_batch(n, deliver_at)
+def _uniform(dev, n, deliver_at, **other_at):
+    templates, tid, data, offs, lens = C.uniform_batch(n, deliver_at, **other_at)
     nif = C.model_netif()
-    want = C.uniform_want(templates, tid, nif, udp_ports=C.UDP_SERVED, tcp_ports=C.TCP_SERVED)
-    recs_h = C.records(templates, nif)[tid]
+    want = C.uniform_want(templates, tid, nif, udp_ports=C.UDP_SERVED, tcp_ports=C.TCP_SERVED, dhcp=True)
+    recs_h = C.uniform_records(templates, tid, nif)
     d, o, ln = _t(dev, data), _t(dev, offs, np.int32), _t(dev, lens, np.int16)
     return want, data, offs, lens, recs_h, (d, o, ln, _t(dev, recs_h.view(np.uint8).reshape(-1, 32)))
 
@@ -214,6 +214,34 @@ def test_batch_past_the_tile_and_the_scan_pass(dev):
     cut = _device(dev, *batch, False, 48 * 7, 8)  # the cut falls in the first tile of the second pass
     C.check_outputs(cut, want, "cut")
     assert int(cut["summary"][:8].view(np.uint32)[1]) == 7
+    _same_as_host(cut, data, offs, lens, recs_h, False)
+
+
+def test_every_kind_and_skips_across_two_scan_passes(dev):
+    """The same size with served TCP, DHCP and overrunning records beside the UDP deliveries, one of
+    each in the last tile of the scan's first pass and in the first tile of its second: every
+    per-kind total and `skipped` is a sum over both passes, and the DHCP count is what is left of
+    the records. Whole, and with the region cut in the first tile of the second pass."""
+    c = C.read_constants()
+    tile, edge = c["kTile"], c["kScanPass"] * c["kTile"]
+    n = edge + 257
+    udp_at = [0, edge - tile, edge - 1, edge, edge + tile - 1, n - 1]
+    tcp_at = [1, 4, tile, edge - tile + 1, edge - 2, edge + 1, edge + tile - 5]
+    dhcp_at = [2, 5, 6, edge - tile + 2, edge - 3, edge + 2, edge + 3, n - 3]
+    overrun_at = [3, 7, 8, 9, tile + 1, edge - tile + 3, edge - 4, edge + 4, n - 4]
+    want, data, offs, lens, recs_h, batch = _uniform(dev, n, udp_at, tcp_at=tcp_at, dhcp_at=dhcp_at, overrun_at=overrun_at)
+    assert [i for i, _ in want.items] == sorted(udp_at + tcp_at + dhcp_at)
+    assert list(want.kind_counts) == [len(udp_at), len(tcp_at), len(dhcp_at)] and want.skipped == len(overrun_at)
+    assert (DM.UDP, DM.TCP, DM.DHCP) == (0, 1, 2)
+    for lo, hi in ((edge - tile, edge), (edge, edge + tile)):  # the last tile of pass one, the first of pass two
+        assert all(any(lo <= i < hi for i in at) for at in (udp_at, tcp_at, dhcp_at, overrun_at))
+    got = _device(dev, *batch, False, (want.total_bytes + 15) & ~15, len(want.recs) + 1)
+    C.check_outputs(got, want, "whole")
+    _same_as_host(got, data, offs, lens, recs_h, False)
+    before = sum(len(r) for (i, _), r in zip(want.items, want.recs) if i < edge + 2)
+    cut = _device(dev, *batch, False, (before + 15) & ~15, len(want.recs))  # the record of frame edge + 2 does not fit
+    C.check_outputs(cut, want, "cut")
+    assert int(cut["summary"][:8].view(np.uint32)[1]) == sum(1 for i, _ in want.items if i < edge + 2)
     _same_as_host(cut, data, offs, lens, recs_h, False)
 
 

@@ -325,3 +325,40 @@ def test_past_the_edges(dev, edge, r, shape):
     assert np.array_equal(index.cpu().numpy().view(np.uint32), want.index_array())
     assert r_.n_skipped == 0
     assert torch.equal(d, torch.from_numpy(data).to(dev)), "the input batch was written"
+
+
+def test_ports_that_differ_in_the_second_scan_pass(dev):
+    """One call over the smallest batch with a second scan pass, three ports and one region of
+    1000 records and 16 bytes: port 0 (sparse before the pass boundary, dense behind it) is cut in
+    the first tile of the second pass, port 1 (every frame) is cut in the first pass, port 2 (few
+    frames, some of them in the second pass) is not cut. Each port's workgroup of the scan carries
+    its own bases and finds its own cut."""
+    import torch
+
+    from halo_amd import egress as E
+
+    c = C.read_constants()
+    tile, edge = c["kTile"], c["kScanPass"] * c["kTile"]
+    n, n_ports, records, index_cap = edge + 257, 3, 1000, 1200
+    i = np.arange(n)
+    masks = np.full(n, 2, np.uint64)                                   # port 1: every frame
+    masks[(i % 300 == 0) | (i >= edge + 10)] |= np.uint64(1)           # port 0: 874 records before the boundary, 247 behind it
+    masks[(i % 1000 == 7) | (i >= edge + 200)] |= np.uint64(4)         # port 2: 320 records
+    sel = [np.flatnonzero((masks >> np.uint64(p)) & np.uint64(1)) for p in range(n_ports)]
+    assert edge <= sel[0][records] < edge + tile and sel[1][records] < edge   # the first record that does not fit
+    assert len(sel[2]) < records and sel[2][-1] >= edge
+    region = 68 * records + 16
+    frames2d, data, offs, lens = C.uniform_batch(n, n)
+    want = EM.egress_uniform(frames2d, masks, n_ports, region, index_cap)
+    assert [int(x) for x in want.ports["frames"]] == [len(s) for s in sel]
+    assert [int(x) for x in want.ports["frames_written"]] == [records, records, len(sel[2])]
+    d, o, ln = _up(dev, data, offs, lens)
+    out, index, skipped = _buffers(dev, n_ports, region, index_cap, skipped0=0)
+    r = E.egress_masks(d, o, ln, torch.from_numpy(masks.view(np.int64)).to(dev), n_ports, region, index_cap, out=out,
+                       skipped=skipped, index=index)
+    torch.cuda.synchronize()
+    assert np.array_equal(r.ports, want.ports), (r.ports, want.ports)
+    exp = torch.from_numpy(want.out(FILL, size=int(out.numel()))).to(dev)
+    assert torch.equal(out, exp), int((out != exp).nonzero()[0])
+    assert np.array_equal(index.cpu().numpy().view(np.uint32), want.index_array())
+    assert r.n_skipped == 0
