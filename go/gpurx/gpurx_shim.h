@@ -24,6 +24,18 @@ _Static_assert(sizeof(halo_deliver_summary_t) == 40, "halo_deliver_summary_t is 
 _Static_assert(offsetof(halo_deliver_summary_t, kind_counts) == 24, "halo_deliver_summary_t.kind_counts");
 _Static_assert(sizeof(halo_deliver_index_t) == 8, "halo_deliver_index_t is 8 bytes");
 _Static_assert(sizeof(halo_deliver_config_t) == 16, "halo_deliver_config_t is 16 bytes");
+// kcp.go's KcpDgram, KcpSeg and KcpSummary
+_Static_assert(sizeof(halo_kcp_dgram_t) == 40, "halo_kcp_dgram_t is 40 bytes");
+_Static_assert(offsetof(halo_kcp_dgram_t, conv0) == 8, "halo_kcp_dgram_t.conv0");
+_Static_assert(offsetof(halo_kcp_dgram_t, first_seg) == 20, "halo_kcp_dgram_t.first_seg");
+_Static_assert(offsetof(halo_kcp_dgram_t, enet_type) == 36, "halo_kcp_dgram_t.enet_type");
+_Static_assert(sizeof(halo_kcp_seg_t) == 32, "halo_kcp_seg_t is 32 bytes");
+_Static_assert(offsetof(halo_kcp_seg_t, data_off) == 24, "halo_kcp_seg_t.data_off");
+_Static_assert(offsetof(halo_kcp_seg_t, check) == 28, "halo_kcp_seg_t.check");
+_Static_assert(sizeof(halo_kcp_summary_t) == 96, "halo_kcp_summary_t is 96 bytes");
+_Static_assert(offsetof(halo_kcp_summary_t, ret_counts) == 16, "halo_kcp_summary_t.ret_counts");
+_Static_assert(offsetof(halo_kcp_summary_t, bytes_hashed) == 56, "halo_kcp_summary_t.bytes_hashed");
+_Static_assert(sizeof(halo_kcp_config_t) == 16, "halo_kcp_config_t is 16 bytes");
 
 // gpurx_netif: a halo_rx_netif_t from NetIf.MacAddr, IpAddrToU(NetIf.IpAddr), NatEnable.
 static inline halo_rx_netif_t gpurx_netif(const uint8_t* mac, uint32_t ip, int nat_enable) {
@@ -33,6 +45,16 @@ static inline halo_rx_netif_t gpurx_netif(const uint8_t* mac, uint32_t ip, int n
     n.ip = ip;
     n.nat_enable = nat_enable ? 1u : 0u;
     return n;
+}
+
+// gpurx_kcp_config: a halo_kcp_config_t (byte_check_mode is HALO_KCP_CHECK_*, -1..2).
+static inline halo_kcp_config_t gpurx_kcp_config(int byte_check_mode, uint32_t port, uint32_t dgram_cap, uint32_t seg_cap) {
+    halo_kcp_config_t c;
+    c.byte_check_mode = byte_check_mode;
+    c.port = port;
+    c.dgram_cap = dgram_cap;
+    c.seg_cap = seg_cap;
+    return c;
 }
 
 // gpurx_parse_one: one frame (l3 = 0) or one bare IPv4 packet (l3 = 1) through the host entry

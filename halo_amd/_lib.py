@@ -179,6 +179,21 @@ DELIVER_KIND = {name: code for code, name in enumerate(DELIVER_KIND_NAMES)}
 DELIVER_KIND_COUNT = len(DELIVER_KIND_NAMES)
 HALO_DELIVER_DHCP = 0x2  # also the bit of halo_deliver_config_t.flags that enables the kind
 DELIVER_NOT_WRITTEN = 0xFFFFFFFF  # an index entry's offset beyond the written prefix
+# KCP ingest: halo_kcp_dgram_t (40 bytes), halo_kcp_seg_t (32), halo_kcp_summary_t (96), HALO_KCP_*
+KCP_DGRAM_DTYPE = np.dtype([("index", "<u4"), ("kind", "u1"), ("conn_type", "u1"), ("ret", "i1"), ("reserved", "u1"),
+                            ("conv0", "<u8"), ("n_segs", "<u2"), ("n_walked", "<u2"), ("first_seg", "<u4"),
+                            ("payload_len", "<u4"), ("session_id", "<u4"), ("conv", "<u4"), ("enet_type", "<u4")])
+KCP_SEG_DTYPE = np.dtype([("dgram", "<u4"), ("cmd", "u1"), ("frg", "u1"), ("wnd", "<u2"), ("ts", "<u4"), ("sn", "<u4"),
+                          ("una", "<u4"), ("len", "<u4"), ("data_off", "<u4"), ("check", "u1"), ("reserved", "u1", (3,))])
+KCP_SUMMARY_DTYPE = np.dtype([("dgrams", "<u4"), ("dgrams_written", "<u4"), ("segs", "<u4"), ("segs_written", "<u4"),
+                              ("ret_counts", "<u4", (5,)), ("enet_counts", "<u4", (4,)), ("ignored", "<u4"),
+                              ("bytes_hashed", "<u8"), ("in_pkts", "<u8"), ("in_bytes", "<u8"), ("in_errs", "<u8"),
+                              ("in_segs", "<u8")])
+assert (KCP_DGRAM_DTYPE.itemsize, KCP_SEG_DTYPE.itemsize, KCP_SUMMARY_DTYPE.itemsize) == (40, 32, 96)
+KCP_CHECK_MODES = {"disabled": -1, "zero": 0, "crc32": 1, "xxh3": 2}  # byte_check_mode (kcp.go:34-41)
+KCP_DGRAM_KCP, KCP_DGRAM_ENET = 0, 1
+KCP_ENET_NAMES = ("ConnEnetSyn", "ConnEnetEst", "ConnEnetFin", "ConnEnetPing")  # conn_type
+KCP_SEG_CHECK_NA, KCP_SEG_CHECK_PASSED, KCP_SEG_CHECK_FAILED = 0, 1, 2
 # halo_rx_ring_scan_t (24 bytes) and HALO_RING_STOP_* / HALO_RING_REGISTER
 RING_SCAN_DTYPE = np.dtype([("n_frames", "<u4"), ("stop", "<u4"), ("end_bytes", "<u8"), ("max_len", "<u4"),
                             ("pad", "<u4")])
@@ -332,6 +347,16 @@ class DeliverConfig(ctypes.Structure):
 
 
 assert ctypes.sizeof(DeliverConfig) == 16
+
+
+class KcpConfig(ctypes.Structure):
+    """halo_kcp_config_t."""
+
+    _fields_ = [("byte_check_mode", ctypes.c_int32), ("port", ctypes.c_uint32), ("dgram_cap", ctypes.c_uint32),
+                ("seg_cap", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(KcpConfig) == 16
 
 
 class BatchDesc(ctypes.Structure):
@@ -544,6 +569,10 @@ _PROTOS = {
         _u8p, ctypes.c_uint64, ctypes.c_void_p]),
     "halo_rx_deliver_host": (ctypes.c_int, [
         ctypes.c_void_p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.POINTER(NetIf), _u8p, _u8p, _u8p, _u8p, _u8p]),
+    "halo_kcp_ingest_workspace": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    "halo_kcp_ingest_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64, ctypes.c_void_p]),
+    "halo_kcp_ingest_host": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     "halo_synth_layout": (ctypes.c_int, [
         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint64)]),

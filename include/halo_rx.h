@@ -1708,6 +1708,134 @@ HALO_API int halo_rx_deliver_host(const halo_deliver_config_t* cfg, const uint8_
                                   const halo_rx_netif_t* netif, const uint32_t* udp_ports, const uint32_t* tcp_ports,
                                   uint8_t* out, halo_deliver_summary_t* summary, halo_deliver_index_t* index);
 
+/* ---- KCP ingest: segment walk and byte check over a delivery stream ---------------------------
+ * The stateless part of the reference's KCP receive path, for the UDP payloads of one served port
+ * in a delivery stream that lies in HBM: what Listener.packetInput (protocol/kcp/session.go:866-921)
+ * and KCP.Input (kcp.go:613-709) do to a datagram's bytes before any session state is touched. A
+ * host then runs Input's state machine from 32-byte segment descriptors whose checks are done, and
+ * touches payload bytes only to hand them on.
+ * INPUT: halo_rx_deliver_*'s stream, summary and index (index_cap entries). Considered: index
+ *   entries k < min(summary.records, index_cap) with offset != 0xFFFFFFFF. SELECTED: those whose
+ *   header says kind == HALO_DELIVER_UDP and local_port == cfg->port. The record count is read
+ *   where the stream lies; the device call sizes its grids from index_cap.
+ * cfg->byte_check_mode (kcp.go:34-41): -1 disabled, 0 zero, 1 CRC32 (IEEE, crc32.ChecksumIEEE), 2
+ *   XXH3 (the low 32 bits of hashcode.GetHashCodeXXH3). The header size H is 28 when disabled,
+ *   else 32 (a u32 hash field follows `length`).
+ * A selected payload of L bytes (packetInput):
+ *   L == 20   ParseEnet (enet.go:100-145): head (bytes 0..3) and tail (16..19) must both be those of
+ *             SYN / EST / FIN / PING -> an ENET datagram record: conn_type, session_id, conv,
+ *             enet_type (big-endian u32 at 4, 8, 12) and conv0 = rawConv, the little-endian u64 of
+ *             bytes 4..11. No match: ignored.
+ *   L >= H    a KCP datagram: conv0 = the little-endian u64 at byte 0 (the listener finds the
+ *             session by it, so the session's kcp.conv == conv0), then Input's walk: while at least
+ *             H bytes remain (a shorter tail is ignored, ret 0) read conv u64, cmd u8, frg u8, wnd
+ *             u16, ts, sn, una, length u32 (and hash u32), advance H, and check in this order
+ *               conv != conv0 -> ret -1;  length > bytes remaining -> -2;  cmd not in 81..84 -> -3;
+ *               mode != -1 and cmd == 81 (PUSH) and hash != byte_check_hash(data[:length]) -> -4
+ *             (zero mode: the field must be 0; a non-PUSH segment is never hashed). A failing check
+ *             ends the datagram; else the segment is PROCESSED (inSegs++) and the walk advances
+ *             `length` bytes. n_segs = processed segments, ret = what Input returns.
+ *   else      ignored. Ignored payloads give no record and are counted.
+ *   The one difference from Input: a client-side session that knows its own conv compares it with
+ *   the record's conv0 itself (Input would return -1 at once; here the walk is relative to conv0).
+ * OUTPUT, all little-endian, all SET (nothing is cleared beforehand):
+ *   halo_kcp_dgram_t [dgram_cap]: one per selected, non-ignored datagram, in stream order.
+ *   halo_kcp_seg_t [seg_cap]: one per WALKED segment — one that passed the conv, length and cmd
+ *     checks, up to the first that fails one — datagrams contiguous and in order: datagram j owns
+ *     [first_seg, first_seg + n_walked) and a consumer uses [first_seg, first_seg + n_segs). The
+ *     entries from n_segs to n_walked (behind a failed byte check) exist so that the hash step runs
+ *     over the plain segment list and needs no second compaction; their `check` is what their own
+ *     hash comparison gave.
+ *   halo_kcp_summary_t: dgrams / segs / ignored are totals over the whole delivery; every other
+ *     counter describes the WRITTEN datagrams (their checks are the ones that ran).
+ * CAPACITY (the egress rule): a datagram record and its segments are written while the datagram
+ *   fits dgram_cap and all its walked segments fit seg_cap; the first datagram that does not fit
+ *   ends the written prefix. Totals stay totals.
+ * READS: nothing outside [0, bytes_written) of the stream rounded up to a 4-byte word, the delivery
+ *   summary and the considered index entries; segment data only as aligned words that hold data
+ *   bytes. The stream is never written. WRITES: exactly the written prefixes and the summary.
+ * The device call is asynchronous on `stream` with no host round trip. Arguments are checked
+ * before any device call. HALO_E_INVAL: a null cfg / summary / deliver_summary; byte_check_mode
+ * outside -1..2; port above 65535; with index_cap > 0 a null stream or index; a null dgrams with
+ * dgram_cap > 0 or segs with seg_cap > 0; for the device call a misaligned array (segs: 16;
+ * dgrams, index, both summaries, workspace: 8; stream: 4) or workspace_bytes <
+ * halo_kcp_ingest_workspace(index_cap, seg_cap). index_cap == 0, or an empty delivery, zeroes the
+ * summary. A build without HIP answers HALO_E_NODEV.
+ * Not covered: sessions, ARQ (parse_ack / parse_data / flush), the ENet handshake, FEC, transmit. */
+#define HALO_KCP_CHECK_DISABLED (-1)
+#define HALO_KCP_CHECK_ZERO 0
+#define HALO_KCP_CHECK_CRC32 1
+#define HALO_KCP_CHECK_XXH3 2
+#define HALO_KCP_DGRAM_KCP 0u
+#define HALO_KCP_DGRAM_ENET 1u
+#define HALO_KCP_ENET_SYN 0u /* conn_type, in ParseEnet's order */
+#define HALO_KCP_ENET_EST 1u
+#define HALO_KCP_ENET_FIN 2u
+#define HALO_KCP_ENET_PING 3u
+#define HALO_KCP_SEG_CHECK_NA 0u     /* not a PUSH segment, or byte check disabled */
+#define HALO_KCP_SEG_CHECK_PASSED 1u
+#define HALO_KCP_SEG_CHECK_FAILED 2u
+typedef struct halo_kcp_config {
+    int32_t byte_check_mode; /* HALO_KCP_CHECK_*                         */
+    uint32_t port;           /* the served UDP port (local_port)         */
+    uint32_t dgram_cap;      /* entries in dgrams                        */
+    uint32_t seg_cap;        /* entries in segs                          */
+} halo_kcp_config_t;         /* 16 B */
+typedef struct halo_kcp_dgram {
+    uint32_t index;       /* k: the datagram's entry in the delivery index                 */
+    uint8_t kind;         /* HALO_KCP_DGRAM_*                                              */
+    uint8_t conn_type;    /* ENET: HALO_KCP_ENET_*; KCP: 0                                 */
+    int8_t ret;           /* KCP: Input's return value, 0 or -1..-4; ENET: 0               */
+    uint8_t reserved;     /* 0                                                             */
+    uint64_t conv0;       /* KCP: LE u64 at byte 0; ENET: rawConv                          */
+    uint16_t n_segs;      /* processed segments (65,507 / 28 < 65,536)                     */
+    uint16_t n_walked;    /* segments with a descriptor, >= n_segs                         */
+    uint32_t first_seg;   /* of its descriptors in segs                                    */
+    uint32_t payload_len; /* L                                                             */
+    uint32_t session_id;  /* ENET fields (0 for KCP)                                       */
+    uint32_t conv;
+    uint32_t enet_type;
+} halo_kcp_dgram_t;       /* 40 B */
+typedef struct halo_kcp_seg {
+    uint32_t dgram;    /* its datagram's position in dgrams                                */
+    uint8_t cmd;       /* 81 PUSH, 82 ACK, 83 WASK, 84 WINS                                */
+    uint8_t frg;
+    uint16_t wnd;
+    uint32_t ts, sn, una;
+    uint32_t len;      /* data bytes                                                       */
+    uint32_t data_off; /* byte offset of the data in the delivery stream                   */
+    uint8_t check;     /* HALO_KCP_SEG_CHECK_*                                             */
+    uint8_t reserved[3]; /* 0 */
+} halo_kcp_seg_t;      /* 32 B */
+typedef struct halo_kcp_summary { /* SET by the call */
+    uint32_t dgrams;         /* selected, non-ignored datagrams, also beyond the capacities  */
+    uint32_t dgrams_written;
+    uint32_t segs;           /* their walked segments                                        */
+    uint32_t segs_written;
+    uint32_t ret_counts[5];  /* written KCP datagrams with ret == -i                         */
+    uint32_t enet_counts[4]; /* written ENET datagrams per conn_type                         */
+    uint32_t ignored;        /* selected payloads that are neither                           */
+    uint64_t bytes_hashed;   /* CRC32 / XXH3: data bytes of the written PUSH descriptors     */
+    uint64_t in_pkts;        /* DefaultSnmp.InPkts / InBytes / KCPInErrors / InSegs as       */
+    uint64_t in_bytes;       /* kcpInput (session.go:722-726) and Input (kcp.go:710, only on */
+    uint64_t in_errs;        /* ret == 0) add them for the written KCP datagrams             */
+    uint64_t in_segs;
+} halo_kcp_summary_t;        /* 96 B */
+/* Bytes of device workspace (8-byte aligned, no initialisation). One workspace serves any number
+ * of calls issued on one stream. */
+HALO_API uint64_t halo_kcp_ingest_workspace(uint32_t index_cap, uint32_t seg_cap);
+HALO_API int halo_kcp_ingest_device(const halo_kcp_config_t* cfg, const uint8_t* d_stream,
+                                    const halo_deliver_summary_t* d_deliver_summary,
+                                    const halo_deliver_index_t* d_index, uint32_t index_cap,
+                                    halo_kcp_dgram_t* d_dgrams, halo_kcp_seg_t* d_segs, halo_kcp_summary_t* d_summary,
+                                    void* d_workspace, uint64_t workspace_bytes, halo_stream_t stream);
+/* The same outputs from the sequential loop over host memory; no HIP. Picked by name, never a
+ * fallback. Arrays need no alignment. */
+HALO_API int halo_kcp_ingest_host(const halo_kcp_config_t* cfg, const uint8_t* stream,
+                                  const halo_deliver_summary_t* deliver_summary, const halo_deliver_index_t* index,
+                                  uint32_t index_cap, halo_kcp_dgram_t* dgrams, halo_kcp_seg_t* segs,
+                                  halo_kcp_summary_t* summary);
+
 /* ---- synthetic traffic (bench + tests; SURVEY.md §8d generator) ----------------------
  * Every field of frame i is a pure function of (seed, i), so any shard of the global
  * stream [first_index, first_index + n) is generated independently.
