@@ -20,7 +20,6 @@
 // scan -> scatter, as the switch's probe / scan / admit kernels are.
 #include <hip/hip_runtime.h>
 
-#include <new>
 #include <shared_mutex>
 #include <vector>
 
@@ -55,10 +54,12 @@ struct ArpGen {
     bool have_routes = false;
 };
 
-struct ArpDevice : Generations<ArpGen> {
+struct ArpDevice : Generations<ArpGen> {  // device_table.h's lifecycle runs it; no stamps, so no fold
     NetIfWord* d_netifs = nullptr;  // HALO_ARP_MAX_NETIFS entries, written once
     std::vector<RouteWord> routes;  // of the last sync: an expiry republishes them
     bool have_routes = false;
+    int write(halo_arp_table* t);
+    void free_arrays();
 };
 
 // The slot holding (netif, ip): its MAC words, or false when the probe chain ends first.
@@ -280,19 +281,17 @@ uint32_t arp_blocks(uint64_t threads) {
     return (uint32_t)(b > kMax ? kMax : (b ? b : 1));
 }
 
-ArpDevice* dev_of(const halo_arp_table* t) { return static_cast<ArpDevice*>(t->dev.load(std::memory_order_acquire)); }
-
 // Compile the host table into the unpublished generation and publish it. The caller holds
-// t->sync_mu and view_mu exclusively and runs on d->device under a ParkResidents.
-int publish_locked(halo_arp_table* t, ArpDevice* d) {
+// t->sync_mu and an Exclusive.
+int ArpDevice::write(halo_arp_table* t) {
     arp::Image img;
     arp::compile(*t, &img);
-    ArpGen* g = d->begin_write();
+    ArpGen* g = begin_write();
     if (!g) return HALO_E_HIP;
     int rc;
     if ((rc = grow(g->d_slots, g->cap, img.slots.size()))) return rc;
-    if (d->have_routes && (rc = grow(g->d_routes, g->routes_cap, d->routes.size() ? d->routes.size() : 1))) return rc;
-    if (!d->d_netifs) {
+    if (have_routes && (rc = grow(g->d_routes, g->routes_cap, routes.size() ? routes.size() : 1))) return rc;
+    if (!d_netifs) {
         NetIfWord w[HALO_ARP_MAX_NETIFS] = {};
         for (uint32_t q = 0; q < t->cfg.n_netifs; ++q) {
             const halo_rx_netif_t& nif = t->cfg.netif[q];
@@ -300,70 +299,42 @@ int publish_locked(halo_arp_table* t, ArpDevice* d) {
             w[q] = NetIfWord{nif.ip, (uint32_t)m[0] | (uint32_t)m[1] << 8 | (uint32_t)m[2] << 16 | (uint32_t)m[3] << 24,
                              (uint32_t)m[4] | (uint32_t)m[5] << 8, nif.nat_enable};
         }
-        if (hipMalloc(&d->d_netifs, sizeof w) != hipSuccess) return HALO_E_NOMEM;
-        if (hipMemcpy(d->d_netifs, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess) return HALO_E_HIP;
+        if (hipMalloc(&d_netifs, sizeof w) != hipSuccess) return HALO_E_NOMEM;
+        if (hipMemcpy(d_netifs, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess) return HALO_E_HIP;
     }
     if (hipMemcpy(g->d_slots, img.slots.data(), img.slots.size() * sizeof(Slot), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
-    if (d->have_routes && !d->routes.empty() &&
-        hipMemcpy(g->d_routes, d->routes.data(), d->routes.size() * sizeof(RouteWord), hipMemcpyHostToDevice) != hipSuccess)
+    if (have_routes && !routes.empty() &&
+        hipMemcpy(g->d_routes, routes.data(), routes.size() * sizeof(RouteWord), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
     g->slots = (uint32_t)img.slots.size();
-    g->n_routes = (uint32_t)d->routes.size();
-    g->have_routes = d->have_routes;
-    if ((rc = d->publish())) return rc;
+    g->n_routes = (uint32_t)routes.size();
+    g->have_routes = have_routes;
+    if ((rc = publish())) return rc;
     arp::mark_synced(*t, img.version);
     return HALO_OK;
 }
 
+void ArpDevice::free_arrays() {
+    for (auto& g : gen) {
+        if (g.d_slots) (void)hipFree(g.d_slots);
+        if (g.d_routes) (void)hipFree(g.d_routes);
+    }
+    if (d_netifs) (void)hipFree(d_netifs);
+}
+
 int ops_sync(halo_arp_table* t, const halo_route_table_t* routes, int device) {
     std::lock_guard<std::mutex> sg(t->sync_mu);
-    ArpDevice* d = dev_of(t);
-    if (d && d->device != device) return HALO_E_INVAL;  // one device per table
+    std::vector<RouteWord> rw;  // ahead of the device object and the parked residents: the walk needs neither
     int rc;
-    if ((rc = device_present(device))) return rc;
-    DeviceScope ds(device);
-    if ((rc = check_device())) return rc;
-    std::vector<RouteWord> rw;
     if (routes && (rc = route_words(routes, &rw, [](const halo_route_entry_t& e) { return RouteWord{e.next_hop, e.netif}; })))
         return rc;
-    if (!d) {
-        d = new (std::nothrow) ArpDevice;
-        if (!d) return HALO_E_NOMEM;
-        d->device = device;
-        t->dev.store(d, std::memory_order_release);
-    }
-    ParkResidents park(device);  // the drains, table growth (hipFree) and copies below
-    std::unique_lock<std::shared_mutex> vl(d->view_mu);  // no lookup between its view and its launch
+    ArpDevice* d;
+    if ((rc = sync_begin(t, device, &d))) return rc;
+    Exclusive x(*d);
     d->routes.swap(rw);
     d->have_routes = routes != nullptr;
-    return publish_locked(t, d);
-}
-
-int ops_publish(halo_arp_table* t) {  // halo_arp_expire after it removed entries, t->sync_mu held
-    ArpDevice* d = dev_of(t);
-    if (!d || !d->published()) return HALO_OK;  // never synced: nothing to rebuild
-    DeviceScope ds(d->device);
-    ParkResidents park(d->device);
-    std::unique_lock<std::shared_mutex> vl(d->view_mu);
-    return publish_locked(t, d);
-}
-
-void ops_destroy(halo_arp_table* t) {
-    ArpDevice* d = dev_of(t);
-    if (!d) return;
-    if (d->device >= 0) {
-        DeviceScope ds(d->device);
-        ParkResidents park(d->device);  // through the frees: hipFree waits for every kernel
-        (void)drain_device(d->device);  // no lookup may still read the tables
-        for (auto& g : d->gen) {
-            if (g.d_slots) (void)hipFree(g.d_slots);
-            if (g.d_routes) (void)hipFree(g.d_routes);
-        }
-        if (d->d_netifs) (void)hipFree(d->d_netifs);
-    }
-    delete d;
-    t->dev.store(nullptr, std::memory_order_release);
+    return d->write(t);
 }
 
 // The view of the published generation; the caller holds view_mu shared until its launch.
@@ -376,7 +347,7 @@ int arp_view(const halo_arp_table* t, ArpDevice* d, ArpView* out) {
 
 int ops_lookup(const halo_arp_table* t, const uint32_t* d_ips, const uint8_t* d_netifs, uint32_t netif, uint32_t n,
                uint8_t* d_mac8, uint8_t* d_verdict, uint32_t* d_miss_count, halo_stream_t stream) {
-    ArpDevice* d = dev_of(t);
+    ArpDevice* d = dev_of<ArpDevice>(t);
     if (!d) return HALO_E_INVAL;  // never synced
     std::shared_lock<std::shared_mutex> lk(d->view_mu);
     ArpView v;
@@ -397,7 +368,7 @@ int ops_encap(const halo_arp_table* t, uint8_t* d_bytes, const uint32_t* d_offse
               const uint32_t* d_route_ids, uint32_t in_netif, bool tx, const uint8_t* d_select,
               const halo_pmflow_via_t* d_via, halo_arp_result_t* d_results, uint32_t* d_counts, uint32_t* d_miss_count,
               halo_stream_t stream) {
-    ArpDevice* d = dev_of(t);
+    ArpDevice* d = dev_of<ArpDevice>(t);
     if (!d) return HALO_E_INVAL;  // never synced
     std::shared_lock<std::shared_mutex> lk(d->view_mu);
     ArpView v;
@@ -445,7 +416,8 @@ int ops_gather(const uint8_t* d_bytes, const uint32_t* d_offsets_dw, const uint1
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }
 
-const arp::DeviceOps kDeviceOps = {ops_sync, ops_publish, ops_destroy, ops_lookup, ops_encap, ops_gather};
+const arp::DeviceOps kDeviceOps = {
+    ops_sync, publish_entry<ArpDevice, halo_arp_table>, destroy<ArpDevice, halo_arp_table>, ops_lookup, ops_encap, ops_gather};
 
 }  // namespace
 

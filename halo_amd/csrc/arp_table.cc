@@ -7,6 +7,8 @@
 
 #include <string.h>
 
+#include "flow_table.h"
+
 #include <new>
 
 using namespace halo::arp;
@@ -78,16 +80,12 @@ void compile(const halo_arp_table& t, Image* out) {
     out->version = t.version;
     for (const auto& kv : t.cache) {
         const uint32_t netif = (uint32_t)(kv.first >> 32), ip = (uint32_t)kv.first;
-        const uint32_t home = key_hash(netif, ip) & mask;
-        uint32_t s = home;
-        while (out->slots[s].tag) s = (s + 1) & mask;  // entries <= capacity < slots: an empty slot exists
+        // entries <= capacity < slots: an empty slot exists
+        const uint32_t s = halo::flowtab::place(out->slots.data(), mask, key_hash(netif, ip) & mask, &out->stats.entries,
+                                                &out->stats.longest_chain, &out->stats.wrapped);
         const uint8_t* m = kv.second.mac;
         out->slots[s] = Slot{ip, kUsed | netif, (uint32_t)m[0] | (uint32_t)m[1] << 8 | (uint32_t)m[2] << 16 | (uint32_t)m[3] << 24,
                              (uint32_t)m[4] | (uint32_t)m[5] << 8};
-        const uint32_t chain = ((s - home) & mask) + 1;
-        ++out->stats.entries;
-        if (chain > out->stats.longest_chain) out->stats.longest_chain = chain;
-        if (s < home) ++out->stats.wrapped;
     }
 }
 

@@ -1,12 +1,16 @@
 // device_table.h — the host side of a device-resident table, shared by the .hip files that keep one
 // (nat_lookup.hip, arp_fwd.hip, pmflow_fwd.hip, route_lpm.hip; switch_fwd.hip takes the device
 // helpers): switching to the table's device, growing a device array, the two generations a sync
-// writes and publishes under lookups in flight, the stamp array two generations share, and the walk
-// over a route table's ids. HIP code only: a *_table.h never includes it, they stay plain C++.
+// writes and publishes under lookups in flight, the stamp array two generations share, the walk
+// over a route table's ids, and the lifecycle of the NAT, ARP and return-flow tables' device copy:
+// Exclusive, fold, sync_begin and the fold / publish / destroy entries. HIP code only: a *_table.h
+// never includes it, they stay plain C++.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <mutex>
+#include <new>
 #include <shared_mutex>
 #include <vector>
 
@@ -134,6 +138,93 @@ int route_words(const halo_route_table_t* routes, std::vector<T>* out, F word) {
         if (rc) return rc;
         out->push_back(word(e));
     }
+}
+
+// The exclusive section of an entry point that writes a table's device copy (a sync, a fold, a
+// publish after an expiry), t->sync_mu held, in the one safe order: run on the table's device; park
+// the resident consumers, so that no ring kernel holds the write lock for its idle window and the
+// drains and hipFree end; then view_mu exclusively: no lookup between its view and its launch.
+struct Exclusive {
+    DeviceScope scope;
+    ParkResidents park;
+    std::unique_lock<std::shared_mutex> lock;
+    template <typename Gen>
+    explicit Exclusive(Generations<Gen>& d) : scope(d.device), park(d.device), lock(d.view_mu) {}
+};
+
+// The lifecycle of a `Table` {sync_mu, std::atomic<void*> dev} whose device copy is a `Dev :
+// Generations<Gen>`. A Dev supplies what differs between the tables: `int write(Table*)`, a
+// generation from a compiled image and its publish(), Exclusive held; `void free_arrays()`, the
+// hipFree of all it allocated, the device drained; and beside a `Stamps stamps` member (ARP has
+// none and is never folded) `merge_stamps(Table&, const uint32_t*, uint32_t)`, the table's own.
+template <typename Dev, typename Table>
+Dev* dev_of(const Table* t) {
+    return static_cast<Dev*>(t->dev.load(std::memory_order_acquire));
+}
+
+// Drain the device and merge the stamps it wrote into the host table. Exclusive held.
+template <typename Dev, typename Table>
+auto fold(Table* t, Dev* d) -> decltype(d->stamps, int()) {
+    if (!d->published()) return HALO_OK;
+    std::vector<uint32_t> back;
+    const int rc = d->stamps.read_back(d->device, &back);
+    if (!rc && !back.empty()) Dev::merge_stamps(*t, back.data(), (uint32_t)back.size());
+    return rc;
+}
+inline int fold(...) { return HALO_OK; }  // a device copy without stamps
+
+// DeviceOps::fold, ahead of an expiry; t->sync_mu held.
+template <typename Dev, typename Table>
+int fold_entry(Table* t) {
+    Dev* d = dev_of<Dev>(t);
+    if (!d) return HALO_OK;
+    Exclusive x(*d);
+    return fold(t, d);
+}
+
+// DeviceOps::publish, after an expiry removed entries; t->sync_mu held.
+template <typename Dev, typename Table>
+int publish_entry(Table* t) {
+    Dev* d = dev_of<Dev>(t);
+    if (!d || !d->published()) return HALO_OK;  // never synced: nothing to rebuild
+    Exclusive x(*d);
+    const int rc = fold(t, d);  // again: a lookup enqueued since the fold may have stamped a flow that stays
+    return rc ? rc : d->write(t);
+}
+
+// The head of a sync, t->sync_mu held: one device per table, the device is there and usable, and
+// the table's device object, which the first sync creates. The caller goes on with `Exclusive x(**out);`.
+template <typename Dev, typename Table>
+int sync_begin(Table* t, int device, Dev** out) {
+    Dev* d = dev_of<Dev>(t);
+    if (d && d->device >= 0 && d->device != device) return HALO_E_INVAL;  // one device per table
+    int rc;
+    if ((rc = device_present(device))) return rc;
+    DeviceScope ds(device);
+    if ((rc = check_device())) return rc;
+    if (!d) {
+        d = new (std::nothrow) Dev;
+        if (!d) return HALO_E_NOMEM;
+        d->device = device;
+        t->dev.store(d, std::memory_order_release);
+    }
+    *out = d;
+    return HALO_OK;
+}
+
+// DeviceOps::destroy: no call on the table is running or will start.
+template <typename Dev, typename Table>
+void destroy(Table* t) {
+    Dev* d = dev_of<Dev>(t);
+    if (!d) return;
+    if (d->device >= 0) {
+        DeviceScope ds(d->device);
+        ParkResidents park(d->device);  // through the frees: hipFree waits for every kernel
+        (void)drain_device(d->device);  // no lookup may still read the tables
+        d->free_arrays();
+    }
+    delete d;
+    t->dev.store(nullptr, std::memory_order_release);
 }
 
 }  // namespace halo

@@ -10,7 +10,9 @@
 // does, hashmap/hashmap.go:63-80) and ends at the first empty slot; tables are rebuilt from
 // scratch by every sync, so there are no tombstones. Two generations, published with
 // release/acquire, under route_lpm.hip's discipline. LastAliveTime is one u32 per flow id in a
-// stamp array both generations share.
+// stamp array both generations share. The extern "C" entry points are nat_table.cc's: they reach
+// this file through nat::device_ops(), and sync, fold, publish and destroy are device_table.h's
+// lifecycle over NatDevice::write and ::free_arrays.
 //
 // Kernel shape: one lane per record, grid-stride by whole wavefronts; a probe reads one aligned
 // 32-byte slot (two 16-byte loads of one 32-byte sector); the port-mapping list (<= 256 entries,
@@ -18,7 +20,6 @@
 // address, a broadcast; misses are counted per wavefront with a ballot and one atomic add.
 #include <hip/hip_runtime.h>
 
-#include <new>
 #include <shared_mutex>
 #include <vector>
 
@@ -49,8 +50,11 @@ struct NatGen {
     uint32_t slots = 0, n_maps = 0;
 };
 
-struct NatDevice : Generations<NatGen> {
+struct NatDevice : Generations<NatGen> {  // device_table.h's lifecycle runs it
     Stamps stamps;
+    static constexpr auto merge_stamps = &nat::merge_stamps;
+    int write(halo_nat_table* t);
+    void free_arrays();
 };
 
 // KIND: HALO_FLOW_NAT_WAN = inbound half (DNAT), HALO_FLOW_NAT_LAN = outbound half (SNAT)
@@ -158,24 +162,14 @@ uint32_t nat_blocks(uint64_t threads) {
     return (uint32_t)(b > kMax ? kMax : (b ? b : 1));
 }
 
-NatDevice* dev_of(const halo_nat_table* t) { return static_cast<NatDevice*>(t->dev.load(std::memory_order_acquire)); }
-
-// Drain the device and merge the stamps it wrote into the host table. view_mu held exclusively.
-int fold_locked(halo_nat_table* t, NatDevice* d) {
-    if (!d->published()) return HALO_OK;
-    std::vector<uint32_t> back;
-    const int rc = d->stamps.read_back(d->device, &back);
-    if (!rc && !back.empty()) nat::merge_stamps(*t, back.data(), (uint32_t)back.size());
-    return rc;
-}
 
 // Compile the host table into the unpublished generation and publish it. The caller holds
-// t->sync_mu and view_mu exclusively, runs on d->device under a ParkResidents, and has folded.
-int publish_locked(halo_nat_table* t, NatDevice* d) {
+// t->sync_mu and an Exclusive, and has folded.
+int NatDevice::write(halo_nat_table* t) {
     nat::Image img;
     int rc = nat::compile(*t, &img, true);
     if (rc) return rc;
-    NatGen* g = d->begin_write();
+    NatGen* g = begin_write();
     if (!g) return HALO_E_HIP;
     for (int k = 0; k < 2; ++k)
         if ((rc = grow(g->d_index[k], g->cap[k], img.slots))) return rc;
@@ -186,51 +180,29 @@ int publish_locked(halo_nat_table* t, NatDevice* d) {
     if (!img.maps.empty() &&
         hipMemcpy(g->d_maps, img.maps.data(), img.maps.size() * sizeof(MapWord), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
-    if ((rc = d->stamps.upload(img.stamps))) return rc;
+    if ((rc = stamps.upload(img.stamps))) return rc;
     g->slots = img.slots;
     g->n_maps = (uint32_t)img.maps.size();
-    return d->publish();
+    return publish();
 }
 
-int ops_fold(halo_nat_table* t) {  // halo_nat_expire, t->sync_mu held
-    NatDevice* d = dev_of(t);
-    if (!d) return HALO_OK;
-    DeviceScope ds(d->device);
-    ParkResidents park(d->device);
-    std::unique_lock<std::shared_mutex> vl(d->view_mu);
-    return fold_locked(t, d);
-}
-
-int ops_publish(halo_nat_table* t) {  // halo_nat_expire after it removed flows, t->sync_mu held
-    NatDevice* d = dev_of(t);
-    if (!d || !d->published()) return HALO_OK;  // never synced: nothing to rebuild
-    DeviceScope ds(d->device);
-    ParkResidents park(d->device);
-    std::unique_lock<std::shared_mutex> vl(d->view_mu);
-    // again: a lookup enqueued since the fold may have stamped a flow that stays
-    const int rc = fold_locked(t, d);
-    return rc ? rc : publish_locked(t, d);
-}
-
-void ops_destroy(halo_nat_table* t) {
-    NatDevice* d = dev_of(t);
-    if (!d) return;
-    if (d->device >= 0) {
-        DeviceScope ds(d->device);
-        ParkResidents park(d->device);  // through the frees: hipFree waits for every kernel
-        (void)drain_device(d->device);  // no lookup may still read the tables
-        for (auto& g : d->gen) {
-            for (auto* p : g.d_index)
-                if (p) (void)hipFree(p);
-            if (g.d_maps) (void)hipFree(g.d_maps);
-        }
-        if (d->stamps.d_stamps) (void)hipFree(d->stamps.d_stamps);
+void NatDevice::free_arrays() {
+    for (auto& g : gen) {
+        for (auto* p : g.d_index)
+            if (p) (void)hipFree(p);
+        if (g.d_maps) (void)hipFree(g.d_maps);
     }
-    delete d;
-    t->dev.store(nullptr, std::memory_order_release);
+    if (stamps.d_stamps) (void)hipFree(stamps.d_stamps);
 }
 
-const nat::DeviceOps kDeviceOps = {ops_fold, ops_publish, ops_destroy};
+int ops_sync(halo_nat_table* t, int device) {  // halo_nat_sync_device, t->sync_mu held
+    NatDevice* d;
+    int rc = sync_begin(t, device, &d);
+    if (rc) return rc;
+    Exclusive x(*d);
+    if ((rc = fold(t, d))) return rc;
+    return d->write(t);
+}
 
 // The view of the published generation; the caller holds view_mu shared until its launch.
 int nat_view(const halo_nat_table* t, NatDevice* d, NatView* out) {
@@ -244,8 +216,7 @@ int nat_view(const halo_nat_table* t, NatDevice* d, NatView* out) {
 template <uint32_t KIND, bool COMPACT>
 int lookup(const halo_nat_table* t, const void* d_records, uint32_t n, uint32_t now, const uint8_t* d_skip,
            halo_tx_op_t* d_ops, uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count, halo_stream_t stream) {
-    if (!t) return HALO_E_INVAL;
-    NatDevice* d = dev_of(t);
+    NatDevice* d = dev_of<NatDevice>(t);
     if (!d) return HALO_E_INVAL;  // never synced
     std::shared_lock<std::shared_mutex> lk(d->view_mu);
     NatView v;
@@ -263,81 +234,34 @@ int lookup(const halo_nat_table* t, const void* d_records, uint32_t n, uint32_t 
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }
 
-}  // namespace
-}  // namespace halo
-
-extern "C" HALO_API int halo_nat_sync_device(halo_nat_table_t* t, int device) {
-    if (!t || device < 0) return HALO_E_INVAL;
-    std::lock_guard<std::mutex> sg(t->sync_mu);
-    halo::NatDevice* d = halo::dev_of(t);
-    if (d && d->device >= 0 && d->device != device) return HALO_E_INVAL;  // one device per table
-    int rc;
-    if ((rc = halo::device_present(device))) return rc;
-    halo::DeviceScope ds(device);
-    if ((rc = halo::check_device())) return rc;
-    if (!d) {
-        d = new (std::nothrow) halo::NatDevice;
-        if (!d) return HALO_E_NOMEM;
-        d->device = device;
-        t->dev_ops = &halo::kDeviceOps;
-        t->dev.store(d, std::memory_order_release);
-    }
-    halo::ParkResidents park(device);  // the drains, table growth (hipFree) and copies below
-    std::unique_lock<std::shared_mutex> vl(d->view_mu);  // no lookup between its view and its launch
-    if ((rc = halo::fold_locked(t, d))) return rc;
-    return halo::publish_locked(t, d);
-}
-
-extern "C" HALO_API int halo_nat_lookup_wan_device(const halo_nat_table_t* t, const halo_rx_result_t* d_records,
-                                                   uint32_t n, uint32_t now, const uint8_t* d_skip, halo_tx_op_t* d_ops,
-                                                   uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
-                                                   halo_stream_t stream) {
-    return halo::lookup<HALO_FLOW_NAT_WAN, false>(t, d_records, n, now, d_skip, d_ops, d_verdict, d_ref, d_miss_count,
-                                                  stream);
-}
-
-extern "C" HALO_API int halo_nat_lookup_lan_device(const halo_nat_table_t* t, const halo_rx_result_t* d_records,
-                                                   uint32_t n, uint32_t now, const uint8_t* d_skip, halo_tx_op_t* d_ops,
-                                                   uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
-                                                   halo_stream_t stream) {
-    return halo::lookup<HALO_FLOW_NAT_LAN, false>(t, d_records, n, now, d_skip, d_ops, d_verdict, d_ref, d_miss_count,
-                                                  stream);
-}
-
-extern "C" HALO_API int halo_nat_lookup_wan_compact_device(const halo_nat_table_t* t,
-                                                           const halo_rx_record16_t* d_records, uint32_t n, uint32_t now,
-                                                           const uint8_t* d_skip, halo_tx_op_t* d_ops,
-                                                           uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
-                                                           halo_stream_t stream) {
-    return halo::lookup<HALO_FLOW_NAT_WAN, true>(t, d_records, n, now, d_skip, d_ops, d_verdict, d_ref, d_miss_count,
-                                                 stream);
-}
-
-extern "C" HALO_API int halo_nat_lookup_lan_compact_device(const halo_nat_table_t* t,
-                                                           const halo_rx_record16_t* d_records, uint32_t n, uint32_t now,
-                                                           const uint8_t* d_skip, halo_tx_op_t* d_ops,
-                                                           uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
-                                                           halo_stream_t stream) {
-    return halo::lookup<HALO_FLOW_NAT_LAN, true>(t, d_records, n, now, d_skip, d_ops, d_verdict, d_ref, d_miss_count,
-                                                 stream);
-}
-
-extern "C" HALO_API int halo_nat_lookup_quote_device(const halo_nat_table_t* t, const halo_rx_result_t* d_quote_records,
-                                                     uint32_t n, halo_tx_deep_nat_t* d_nat, halo_stream_t stream) {
-    if (!t) return HALO_E_INVAL;
-    halo::NatDevice* d = halo::dev_of(t);
+int ops_quote(const halo_nat_table* t, const halo_rx_result_t* d_quote_records, uint32_t n, halo_tx_deep_nat_t* d_nat,
+              halo_stream_t stream) {
+    NatDevice* d = dev_of<NatDevice>(t);
     if (!d) return HALO_E_INVAL;  // never synced
     std::shared_lock<std::shared_mutex> lk(d->view_mu);
-    halo::NatView v;
-    if (halo::nat_view(t, d, &v)) return HALO_E_INVAL;
+    NatView v;
+    if (nat_view(t, d, &v)) return HALO_E_INVAL;
     if (!d_nat) return HALO_E_INVAL;
     if (n == 0) return HALO_OK;
     if (!d_quote_records) return HALO_E_INVAL;
     if ((reinterpret_cast<uintptr_t>(d_quote_records) & 15u) || (reinterpret_cast<uintptr_t>(d_nat) & 7u))
         return HALO_E_INVAL;
-    int rc = halo::check_device();
+    int rc = check_device();
     if (rc) return rc;
-    hipLaunchKernelGGL(halo::nat_quote_kernel, dim3(halo::nat_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       v, d_quote_records, n, d_nat);
+    hipLaunchKernelGGL(nat_quote_kernel, dim3(nat_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), v,
+                       d_quote_records, n, d_nat);
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }
+
+// (the lookups in DeviceOps' order: the kernels are emitted in the order they are first named)
+const nat::DeviceOps kDeviceOps = {
+    ops_sync, fold_entry<NatDevice, halo_nat_table>, publish_entry<NatDevice, halo_nat_table>, destroy<NatDevice, halo_nat_table>,
+    lookup<HALO_FLOW_NAT_WAN, false>, lookup<HALO_FLOW_NAT_LAN, false>, lookup<HALO_FLOW_NAT_WAN, true>, lookup<HALO_FLOW_NAT_LAN, true>,
+    ops_quote};
+
+}  // namespace
+
+namespace nat {
+const DeviceOps* device_ops() { return &kDeviceOps; }
+}  // namespace nat
+}  // namespace halo

@@ -1,7 +1,8 @@
 // nat_table.cc — the host control plane of the NAT flow table (include/halo_rx.h, "NAT flow
 // table"): NatAddFlow, NatGetFlowByHash / ByWan, CheckNatPortMapping, NatTableClear and ListNat of
 // engine/ipv4_engine.go:524-759 restated over std containers, the slow path for device misses,
-// and the compile of both indexes into the open-addressing image nat_lookup.hip uploads. No HIP.
+// and the compile of both indexes into the open-addressing image nat_lookup.hip uploads. The
+// device side is reached through nat::DeviceOps. No HIP.
 #include "nat_table.h"
 
 #include <string.h>
@@ -104,19 +105,8 @@ int check_mapping(const halo_nat_table& t, uint32_t dir, uint32_t ip, uint32_t p
     return -1;
 }
 
-inline bool later(uint32_t a, uint32_t b) { return (int32_t)(a - b) > 0; }
-
-void place(std::vector<Slot>& idx, uint32_t mask, const Key& k, uint32_t x_ip, uint32_t x_port, uint32_t id,
-           uint32_t* longest, uint32_t* wrapped) {
-    const uint32_t home = home_slot(k, mask);
-    uint32_t s = home, chain = 1;
-    while (idx[s].tag) {
-        s = (s + 1) & mask;
-        ++chain;
-    }
-    idx[s] = Slot{k.rip, k.lip, k.rport | k.lport << 16, kSlotUsed | k.proto, x_ip, x_port, id, 0};
-    if (chain > *longest) *longest = chain;
-    if (s < home) ++*wrapped;
+const DeviceOps* dev_ops(const halo_nat_table* t) {  // null: host-only build, or never synced
+    return t->dev.load(std::memory_order_acquire) && device_ops ? device_ops() : nullptr;
 }
 
 }  // namespace
@@ -124,31 +114,24 @@ void place(std::vector<Slot>& idx, uint32_t mask, const Key& k, uint32_t x_ip, u
 int compile(const halo_nat_table& t, Image* out, bool with_stamps) {
     std::lock_guard<std::mutex> g(t.mu);
     const uint32_t n_lan = t.n_lan, n_wan = (uint32_t)t.wan.size();
-    const uint32_t most = n_lan > n_wan ? n_lan : n_wan;
-    uint32_t log2 = t.cfg.capacity_log2;
-    if (log2 == 0) {
-        log2 = 4;  // load <= 0.5
-        while (log2 < 31 && (1ull << log2) < 2ull * most) ++log2;
-        if (log2 > 28) return HALO_E_RANGE;
-    } else if (most >= (1u << log2)) {
-        return HALO_E_RANGE;  // a probe chain must end at an empty slot
-    }
-    out->slots = 1u << log2;
+    const int rc = flowtab::capacity_slots(t.cfg.capacity_log2, n_lan > n_wan ? n_lan : n_wan, &out->slots);
+    if (rc) return rc;
     const uint32_t mask = out->slots - 1;
     halo_nat_layout_stats_t st{};
     st.slots = out->slots;
     st.port_mappings = (uint32_t)t.maps.size();
     for (auto& v : out->index) v.assign(out->slots, Slot{});
+    const auto put = [&](uint32_t dir, const Key& k, uint32_t x_ip, uint32_t x_port, uint32_t id) {
+        Slot* idx = out->index[dir].data();
+        const uint32_t s = flowtab::place(idx, mask, flowtab::home_slot(k, mask), &st.entries[dir], &st.longest_chain[dir],
+                                          &st.wrapped[dir]);
+        idx[s] = Slot{k.rip, k.lip, k.rport | k.lport << 16, kSlotUsed | k.proto, x_ip, x_port, id, 0};
+    };
     for (const auto& kv : t.flows) {  // ascending id: the layout depends on the table's history only
         const halo_nat_flow_t& f = kv.second.f;
-        if (kv.second.in_lan) {
-            place(out->index[HALO_FLOW_NAT_LAN], mask, Key{f.remote_ip, f.remote_port, f.lan_ip, f.lan_port, f.proto},
-                  f.wan_ip, f.wan_port, f.id, &st.longest_chain[0], &st.wrapped[0]);
-            ++st.entries[0];
-        }
-        place(out->index[HALO_FLOW_NAT_WAN], mask, Key{f.remote_ip, f.remote_port, f.wan_ip, f.wan_port, f.proto},
-              f.lan_ip, f.lan_port, f.id, &st.longest_chain[1], &st.wrapped[1]);
-        ++st.entries[1];
+        if (kv.second.in_lan)
+            put(HALO_FLOW_NAT_LAN, Key{f.remote_ip, f.remote_port, f.lan_ip, f.lan_port, f.proto}, f.wan_ip, f.wan_port, f.id);
+        put(HALO_FLOW_NAT_WAN, Key{f.remote_ip, f.remote_port, f.wan_ip, f.wan_port, f.proto}, f.lan_ip, f.lan_port, f.id);
     }
     out->maps.clear();
     for (const PortMapping& e : t.maps)
@@ -164,10 +147,7 @@ int compile(const halo_nat_table& t, Image* out, bool with_stamps) {
 
 void merge_stamps(halo_nat_table& t, const uint32_t* dev, uint32_t n) {
     std::lock_guard<std::mutex> g(t.mu);
-    for (auto& kv : t.flows) {
-        if (kv.first >= n) break;
-        if (later(dev[kv.first], kv.second.f.last_alive)) kv.second.f.last_alive = dev[kv.first];
-    }
+    flowtab::merge_stamps(t.flows, dev, n, [](Flow& fl) -> uint32_t& { return fl.f.last_alive; });
 }
 
 }  // namespace nat
@@ -185,7 +165,7 @@ extern "C" HALO_API int halo_nat_table_create(const halo_nat_config_t* cfg, halo
 
 extern "C" HALO_API int halo_nat_table_destroy(halo_nat_table_t* t) {
     if (!t) return HALO_E_INVAL;
-    if (t->dev_ops) t->dev_ops->destroy(t);
+    if (const DeviceOps* ops = dev_ops(t)) ops->destroy(t);
     delete t;
     return HALO_OK;
 }
@@ -292,8 +272,9 @@ extern "C" HALO_API int halo_nat_expire(halo_nat_table_t* t, uint32_t now, uint3
     if (!t) return HALO_E_INVAL;
     if (n_removed) *n_removed = 0;
     std::lock_guard<std::mutex> sg(t->sync_mu);
+    const DeviceOps* ops = dev_ops(t);
     int rc;
-    if (t->dev_ops && (rc = t->dev_ops->fold(t))) return rc;
+    if (ops && (rc = ops->fold(t))) return rc;
     uint32_t removed = 0;
     {
         std::lock_guard<std::mutex> g(t->mu);
@@ -317,8 +298,8 @@ extern "C" HALO_API int halo_nat_expire(halo_nat_table_t* t, uint32_t now, uint3
         }
     }
     if (n_removed) *n_removed = removed;
-    if (removed && t->dev_ops && (rc = t->dev_ops->publish(t))) return rc;
-    return HALO_OK;
+    // the device must stop answering with the flows that left
+    return removed && ops ? ops->publish(t) : HALO_OK;
 }
 
 extern "C" HALO_API int halo_nat_list(const halo_nat_table_t* t, halo_nat_flow_t* out, uint32_t cap, uint32_t* n) {
@@ -341,4 +322,33 @@ extern "C" HALO_API int halo_nat_layout_stats(const halo_nat_table_t* t, halo_na
     if (rc) return rc;
     *out = img.stats;
     return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_sync_device(halo_nat_table_t* t, int device) {
+    if (!t || device < 0) return HALO_E_INVAL;
+    if (!device_ops) return HALO_E_NODEV;
+    std::lock_guard<std::mutex> sg(t->sync_mu);
+    return device_ops()->sync(t, device);
+}
+
+// halo_nat_lookup_wan_device, halo_nat_lookup_lan_device, halo_nat_lookup_wan_compact_device and
+// halo_nat_lookup_lan_compact_device: halo_nat_lookup_<WHICH>_device over RECORD is DeviceOps::lookup_<WHICH>.
+#define HALO_NAT_LOOKUP(WHICH, RECORD)                                                                                  \
+    extern "C" HALO_API int halo_nat_lookup_##WHICH##_device(                                                           \
+        const halo_nat_table_t* t, const RECORD* d_records, uint32_t n, uint32_t now, const uint8_t* d_skip,            \
+        halo_tx_op_t* d_ops, uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count, halo_stream_t stream) {       \
+        if (!t) return HALO_E_INVAL;                                                                                    \
+        if (!device_ops) return HALO_E_NODEV;                                                                           \
+        return device_ops()->lookup_##WHICH(t, d_records, n, now, d_skip, d_ops, d_verdict, d_ref, d_miss_count, stream); \
+    }
+HALO_NAT_LOOKUP(wan, halo_rx_result_t)
+HALO_NAT_LOOKUP(lan, halo_rx_result_t)
+HALO_NAT_LOOKUP(wan_compact, halo_rx_record16_t)
+HALO_NAT_LOOKUP(lan_compact, halo_rx_record16_t)
+#undef HALO_NAT_LOOKUP
+
+extern "C" HALO_API int halo_nat_lookup_quote_device(const halo_nat_table_t* t, const halo_rx_result_t* d_quote_records,
+                                                     uint32_t n, halo_tx_deep_nat_t* d_nat, halo_stream_t stream) {
+    if (!t) return HALO_E_INVAL;
+    return device_ops ? device_ops()->quote(t, d_quote_records, n, d_nat, stream) : HALO_E_NODEV;
 }

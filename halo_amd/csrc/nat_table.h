@@ -1,6 +1,8 @@
 // nat_table.h — the host control plane of a NATing NetIf's flow table (nat_table.cc) and the
 // image of it that nat_lookup.hip uploads. Plain C++17, no HIP: nat_table.cc compiles alone with
-// g++ (tools/fuzz_nat.cc drives it under ASan/UBSan) and into libhalo_rx.so.
+// g++ (tools/fuzz_nat.cc drives it under ASan/UBSan) and into libhalo_rx.so. Every extern "C" entry
+// point is nat_table.cc's; the device side is reached through nat::DeviceOps, as the ARP, switch
+// and return-flow tables reach theirs. Hash, placement and capacity rule are flow_table.h's.
 //
 // Reference state (engine/ipv4_engine.go:423-759), kept as the reference builds it:
 //   NatFlowTable     lan : normalised NatFlowHash    -> flow      (ListNat / NatTableClear walk it)
@@ -19,19 +21,13 @@
 #include <vector>
 
 #include "../../include/halo_rx.h"
-#include "flow_key.h"
+#include "flow_table.h"
 
 namespace halo {
 namespace nat {
 
-struct KeyHash {
-    size_t operator()(const flowkey::Key& k) const { return (size_t)flowkey::key_hash(k); }
-};
-struct KeyEq {
-    bool operator()(const flowkey::Key& a, const flowkey::Key& b) const {
-        return a.rip == b.rip && a.rport == b.rport && a.lip == b.lip && a.lport == b.lport && a.proto == b.proto;
-    }
-};
+using flowtab::KeyEq;
+using flowtab::KeyHash;
 
 struct Flow {
     halo_nat_flow_t f;
@@ -73,9 +69,6 @@ struct MapWord {
     uint32_t proto;
 };
 
-// home slot of a key: the hash of halo_flow_hash_device, low bits
-inline uint32_t home_slot(const flowkey::Key& k, uint32_t mask) { return (uint32_t)flowkey::key_hash(k) & mask; }
-
 struct Image {
     uint32_t slots = 0;          // per index
     std::vector<Slot> index[2];  // [HALO_FLOW_NAT_LAN], [HALO_FLOW_NAT_WAN]
@@ -86,10 +79,19 @@ struct Image {
 
 // The device side of a table (nat_lookup.hip); nat_table.cc reaches it only through these.
 struct DeviceOps {
-    int (*fold)(halo_nat_table* t);     // drain the device, merge its stamps into the host table
-    int (*publish)(halo_nat_table* t);  // compile and publish a new generation
+    int (*sync)(halo_nat_table* t, int device);  // t->sync_mu held, as for fold and publish
+    int (*fold)(halo_nat_table* t);              // drain the device, merge its stamps into the host table
+    int (*publish)(halo_nat_table* t);           // rebuild the copy after an expiry
     void (*destroy)(halo_nat_table* t);
+    using Lookup = int (*)(const halo_nat_table* t, const void* d_records, uint32_t n, uint32_t now, const uint8_t* d_skip,
+                           halo_tx_op_t* d_ops, uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_miss_count,
+                           halo_stream_t stream);
+    Lookup lookup_wan, lookup_lan, lookup_wan_compact, lookup_lan_compact;  // compact: d_records are halo_rx_record16_t
+    int (*quote)(const halo_nat_table* t, const halo_rx_result_t* d_quote_records, uint32_t n, halo_tx_deep_nat_t* d_nat,
+                 halo_stream_t stream);
 };
+// Defined by nat_lookup.hip; absent (null) in a host-only build, where the device calls are HALO_E_NODEV.
+const DeviceOps* device_ops() __attribute__((weak));
 
 }  // namespace nat
 }  // namespace halo
@@ -105,8 +107,7 @@ struct halo_nat_table {
     uint32_t n_lan = 0;  // flows with in_lan (== lan.size())
     // device copy (nat_lookup.hip)
     std::mutex sync_mu;  // one sync / expire at a time
-    std::atomic<void*> dev{nullptr};                 // set once by the first sync (release)
-    const halo::nat::DeviceOps* dev_ops = nullptr;  // written and read under sync_mu
+    std::atomic<void*> dev{nullptr};  // set once by the first sync (release)
 };
 
 namespace halo {

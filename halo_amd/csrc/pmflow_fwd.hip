@@ -20,7 +20,6 @@
 // flag byte per frame, so the scatter does not probe again.
 #include <hip/hip_runtime.h>
 
-#include <new>
 #include <shared_mutex>
 #include <vector>
 
@@ -60,11 +59,14 @@ struct PmGen {
     bool have_routes = false;
 };
 
-struct PmDevice : Generations<PmGen> {
+struct PmDevice : Generations<PmGen> {  // device_table.h's lifecycle runs it
     NetIfWord* d_netifs = nullptr;  // HALO_ARP_MAX_NETIFS entries, written once
     Stamps stamps;
     std::vector<uint32_t> routes;  // of the last sync: an expiry republishes them
     bool have_routes = false;
+    static constexpr auto merge_stamps = &pmflow::merge_stamps;
+    int write(halo_pmflow_table* t);
+    void free_arrays();
 };
 
 __global__ void __launch_bounds__(256) pmflow_lookup_kernel(const PmView v, const halo_rx_result_t* __restrict__ recs,
@@ -213,108 +215,58 @@ uint32_t pm_blocks(uint64_t threads) {
     return (uint32_t)(b > kMax ? kMax : (b ? b : 1));
 }
 
-PmDevice* dev_of(const halo_pmflow_table* t) { return static_cast<PmDevice*>(t->dev.load(std::memory_order_acquire)); }
-
-// Drain the device and merge the stamps it wrote into the host table. view_mu held exclusively.
-int fold_locked(halo_pmflow_table* t, PmDevice* d) {
-    if (!d->published()) return HALO_OK;
-    std::vector<uint32_t> back;
-    const int rc = d->stamps.read_back(d->device, &back);
-    if (!rc && !back.empty()) pmflow::merge_stamps(*t, back.data(), (uint32_t)back.size());
-    return rc;
-}
-
 // Compile the host table into the unpublished generation and publish it. The caller holds
-// t->sync_mu and view_mu exclusively, runs on d->device under a ParkResidents, and has folded.
-int publish_locked(halo_pmflow_table* t, PmDevice* d) {
+// t->sync_mu and an Exclusive, and has folded.
+int PmDevice::write(halo_pmflow_table* t) {
     pmflow::Image img;
     int rc = pmflow::compile(*t, &img, true);
     if (rc) return rc;
-    PmGen* g = d->begin_write();
+    PmGen* g = begin_write();
     if (!g) return HALO_E_HIP;
     if ((rc = grow(g->d_slots, g->cap, img.slots.size()))) return rc;
-    if (d->have_routes && (rc = grow(g->d_routes, g->routes_cap, d->routes.size() ? d->routes.size() : 1))) return rc;
-    if (!d->d_netifs) {
+    if (have_routes && (rc = grow(g->d_routes, g->routes_cap, routes.size() ? routes.size() : 1))) return rc;
+    if (!d_netifs) {
         NetIfWord w[HALO_ARP_MAX_NETIFS] = {};
         for (uint32_t q = 0; q < t->cfg.n_netifs; ++q)
             w[q] = NetIfWord{t->cfg.netif[q].ip, t->cfg.netif[q].nat_enable ? 1u : 0u, t->cfg.gateway[q], 0};
-        if (hipMalloc(&d->d_netifs, sizeof w) != hipSuccess) return HALO_E_NOMEM;
-        if (hipMemcpy(d->d_netifs, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess) return HALO_E_HIP;
+        if (hipMalloc(&d_netifs, sizeof w) != hipSuccess) return HALO_E_NOMEM;
+        if (hipMemcpy(d_netifs, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess) return HALO_E_HIP;
     }
     if (hipMemcpy(g->d_slots, img.slots.data(), img.slots.size() * sizeof(Slot), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
-    if (d->have_routes && !d->routes.empty() &&
-        hipMemcpy(g->d_routes, d->routes.data(), d->routes.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
+    if (have_routes && !routes.empty() &&
+        hipMemcpy(g->d_routes, routes.data(), routes.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
         return HALO_E_HIP;
-    if ((rc = d->stamps.upload(img.stamps))) return rc;
+    if ((rc = stamps.upload(img.stamps))) return rc;
     g->slots = (uint32_t)img.slots.size();
-    g->n_routes = (uint32_t)d->routes.size();
-    g->have_routes = d->have_routes;
-    if ((rc = d->publish())) return rc;
+    g->n_routes = (uint32_t)routes.size();
+    g->have_routes = have_routes;
+    if ((rc = publish())) return rc;
     pmflow::mark_synced(*t, img.version);
     return HALO_OK;
 }
 
+void PmDevice::free_arrays() {
+    for (auto& g : gen) {
+        if (g.d_slots) (void)hipFree(g.d_slots);
+        if (g.d_routes) (void)hipFree(g.d_routes);
+    }
+    if (d_netifs) (void)hipFree(d_netifs);
+    if (stamps.d_stamps) (void)hipFree(stamps.d_stamps);
+}
+
 int ops_sync(halo_pmflow_table* t, const halo_route_table_t* routes, int device) {
     std::lock_guard<std::mutex> sg(t->sync_mu);
-    PmDevice* d = dev_of(t);
-    if (d && d->device != device) return HALO_E_INVAL;  // one device per table
+    std::vector<uint32_t> rw;  // ahead of the device object and the parked residents: the walk needs neither
     int rc;
-    if ((rc = device_present(device))) return rc;
-    DeviceScope ds(device);
-    if ((rc = check_device())) return rc;
-    std::vector<uint32_t> rw;
     if (routes && (rc = route_words(routes, &rw, [](const halo_route_entry_t& e) { return e.netif; }))) return rc;
-    if (!d) {
-        d = new (std::nothrow) PmDevice;
-        if (!d) return HALO_E_NOMEM;
-        d->device = device;
-        t->dev.store(d, std::memory_order_release);
-    }
-    ParkResidents park(device);  // the drains, table growth (hipFree) and copies below
-    std::unique_lock<std::shared_mutex> vl(d->view_mu);  // no lookup between its view and its launch
-    if ((rc = fold_locked(t, d))) return rc;
+    PmDevice* d;
+    if ((rc = sync_begin(t, device, &d))) return rc;
+    Exclusive x(*d);
+    if ((rc = fold(t, d))) return rc;
     d->routes.swap(rw);
     d->have_routes = routes != nullptr;
-    return publish_locked(t, d);
-}
-
-int ops_fold(halo_pmflow_table* t) {  // halo_pmflow_expire, t->sync_mu held
-    PmDevice* d = dev_of(t);
-    if (!d) return HALO_OK;
-    DeviceScope ds(d->device);
-    ParkResidents park(d->device);
-    std::unique_lock<std::shared_mutex> vl(d->view_mu);
-    return fold_locked(t, d);
-}
-
-int ops_publish(halo_pmflow_table* t) {  // halo_pmflow_expire after it removed flows, t->sync_mu held
-    PmDevice* d = dev_of(t);
-    if (!d || !d->published()) return HALO_OK;  // never synced: nothing to rebuild
-    DeviceScope ds(d->device);
-    ParkResidents park(d->device);
-    std::unique_lock<std::shared_mutex> vl(d->view_mu);
-    // again: a lookup enqueued since the fold may have stamped a flow that stays
-    const int rc = fold_locked(t, d);
-    return rc ? rc : publish_locked(t, d);
-}
-
-void ops_destroy(halo_pmflow_table* t) {
-    PmDevice* d = dev_of(t);
-    if (!d) return;
-    if (d->device >= 0) {
-        DeviceScope ds(d->device);
-        ParkResidents park(d->device);  // through the frees: hipFree waits for every kernel
-        (void)drain_device(d->device);  // no lookup may still read the tables
-        for (auto& g : d->gen) {
-            if (g.d_slots) (void)hipFree(g.d_slots);
-            if (g.d_routes) (void)hipFree(g.d_routes);
-        }
-        if (d->d_netifs) (void)hipFree(d->d_netifs);
-        if (d->stamps.d_stamps) (void)hipFree(d->stamps.d_stamps);
-    }
-    delete d;
-    t->dev.store(nullptr, std::memory_order_release);
+    return d->write(t);
 }
 
 // The view of the published generation; the caller holds view_mu shared until its launch.
@@ -329,7 +281,7 @@ int pm_view(const halo_pmflow_table* t, PmDevice* d, PmView* out) {
 int ops_lookup(const halo_pmflow_table* t, const halo_rx_result_t* d_records, uint32_t n, uint32_t now,
                const uint32_t* d_route_ids, const uint8_t* d_select, halo_tx_op_t* d_ops, halo_pmflow_via_t* d_via,
                uint8_t* d_hit, uint32_t* d_counts, halo_stream_t stream) {
-    PmDevice* d = dev_of(t);
+    PmDevice* d = dev_of<PmDevice>(t);
     if (!d) return HALO_E_INVAL;  // never synced
     std::shared_lock<std::shared_mutex> lk(d->view_mu);
     PmView v;
@@ -346,7 +298,7 @@ int ops_record(const halo_pmflow_table* t, uint32_t in_netif, const halo_rx_resu
                const uint8_t* d_wan_verdict, const halo_tx_op_t* d_ops, const halo_arp_result_t* d_arp_results, uint32_t n,
                uint32_t now, halo_pmflow_item_t* d_items, uint32_t cap, uint32_t* d_count, void* d_workspace,
                halo_stream_t stream) {
-    PmDevice* d = dev_of(t);
+    PmDevice* d = dev_of<PmDevice>(t);
     if (!d) return HALO_E_INVAL;  // never synced
     std::shared_lock<std::shared_mutex> lk(d->view_mu);
     PmView v;
@@ -375,7 +327,9 @@ int ops_arp_drop(halo_arp_result_t* d_results, const uint32_t* d_index, uint32_t
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }
 
-const pmflow::DeviceOps kDeviceOps = {ops_sync, ops_fold, ops_publish, ops_destroy, ops_lookup, ops_record, ops_arp_drop};
+const pmflow::DeviceOps kDeviceOps = {
+    ops_sync, fold_entry<PmDevice, halo_pmflow_table>, publish_entry<PmDevice, halo_pmflow_table>, destroy<PmDevice, halo_pmflow_table>,
+    ops_lookup, ops_record, ops_arp_drop};
 
 }  // namespace
 

@@ -14,8 +14,6 @@ using namespace halo::pmflow;
 
 namespace {
 
-inline bool later(uint32_t a, uint32_t b) { return (int32_t)(a - b) > 0; }
-
 void store_entry(const Flow& f, halo_pmflow_entry_t* out) {
     out->remote_ip = f.key.rip;
     out->lan_ip = f.key.lip;
@@ -37,32 +35,19 @@ namespace pmflow {
 
 int compile(const halo_pmflow_table& t, Image* out, bool with_stamps) {
     std::lock_guard<std::mutex> g(t.mu);
-    const uint32_t n = (uint32_t)t.flows.size();
-    uint32_t log2 = t.cfg.capacity_log2;
-    if (log2 == 0) {
-        log2 = 4;  // load <= 0.5
-        while (log2 < 31 && (1ull << log2) < 2ull * n) ++log2;
-        if (log2 > 28) return HALO_E_RANGE;
-    } else if (n >= (1u << log2)) {
-        return HALO_E_RANGE;  // a probe chain must end at an empty slot
-    }
-    const uint32_t slots = 1u << log2, mask = slots - 1;
+    uint32_t slots;
+    const int rc = flowtab::capacity_slots(t.cfg.capacity_log2, (uint32_t)t.flows.size(), &slots);
+    if (rc) return rc;
+    const uint32_t mask = slots - 1;
     out->slots.assign(slots, Slot{});
     out->stats = halo_pmflow_layout_stats_t{slots, 0, 0, 0};
     out->version = t.version;
     for (const auto& kv : t.flows) {  // ascending id: the layout depends on the table's history only
         const Flow& f = kv.second;
-        const uint32_t home = home_slot(f.key, mask);
-        uint32_t s = home, chain = 1;
-        while (out->slots[s].tag) {
-            s = (s + 1) & mask;
-            ++chain;
-        }
+        const uint32_t s = flowtab::place(out->slots.data(), mask, flowtab::home_slot(f.key, mask), &out->stats.entries,
+                                          &out->stats.longest_chain, &out->stats.wrapped);
         out->slots[s] = Slot{f.key.rip, f.key.lip, f.key.rport | f.key.lport << 16, kSlotUsed | f.key.proto,
                              f.wan_netif, f.wan_port, f.id, 0};
-        ++out->stats.entries;
-        if (chain > out->stats.longest_chain) out->stats.longest_chain = chain;
-        if (s < home) ++out->stats.wrapped;
     }
     out->stamps.clear();
     if (with_stamps) {
@@ -74,10 +59,7 @@ int compile(const halo_pmflow_table& t, Image* out, bool with_stamps) {
 
 void merge_stamps(halo_pmflow_table& t, const uint32_t* dev, uint32_t n) {
     std::lock_guard<std::mutex> g(t.mu);
-    for (auto& kv : t.flows) {
-        if (kv.first >= n) break;
-        if (later(dev[kv.first], kv.second.last_alive)) kv.second.last_alive = dev[kv.first];
-    }
+    flowtab::merge_stamps(t.flows, dev, n, [](Flow& f) -> uint32_t& { return f.last_alive; });
 }
 
 void mark_synced(halo_pmflow_table& t, uint64_t v) {

@@ -1,7 +1,8 @@
 // pmflow_table.h — the port-mapping return-flow table (include/halo_rx.h, "port-mapping return
 // flows"): the host control plane (pmflow_table.cc) and the slot layout the device side
 // (pmflow_fwd.hip) shares with the host compile. Plain C++17, no HIP: pmflow_table.cc compiles
-// alone with g++ (tools/fuzz_pmflow.cc drives it under ASan/UBSan) and into libhalo_rx.so.
+// alone with g++ (tools/fuzz_pmflow.cc drives it under ASan/UBSan) and into libhalo_rx.so. Hash,
+// placement, capacity rule and stamp merge are flow_table.h's, shared with the NAT flow table.
 //
 // Reference state (engine/ipv4_engine.go:489-516, engine/engine.go): Router.NatPortMappingFlowTable,
 // NatFlowHash -> NatPortMappingFlow {WanNetIf, WanPort, LastAliveTime}, every flow allocated from
@@ -16,19 +17,13 @@
 #include <vector>
 
 #include "../../include/halo_rx.h"
-#include "flow_key.h"
+#include "flow_table.h"
 
 namespace halo {
 namespace pmflow {
 
-struct KeyHash {
-    size_t operator()(const flowkey::Key& k) const { return (size_t)flowkey::key_hash(k); }
-};
-struct KeyEq {
-    bool operator()(const flowkey::Key& a, const flowkey::Key& b) const {
-        return a.rip == b.rip && a.rport == b.rport && a.lip == b.lip && a.lport == b.lport && a.proto == b.proto;
-    }
-};
+using flowtab::KeyEq;
+using flowtab::KeyHash;
 
 struct Flow {
     flowkey::Key key;
@@ -57,8 +52,6 @@ struct alignas(16) NetIfWord {
     uint32_t gateway;
     uint32_t pad;
 };
-
-inline uint32_t home_slot(const flowkey::Key& k, uint32_t mask) { return (uint32_t)flowkey::key_hash(k) & mask; }
 
 // halo_pmflow_record_device's count / scan / scatter: frames per workgroup, as arp_fwd.hip's gather
 // has them (the scan's pass is tile_scan.h's).

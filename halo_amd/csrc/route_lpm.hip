@@ -225,10 +225,7 @@ extern "C" HALO_API int halo_route_sync_device(halo_route_table_t* t, int device
     if (!t || device < 0) return HALO_E_INVAL;
     if (t->dev.device >= 0 && t->dev.device != device) return HALO_E_INVAL;  // one device per table
     int rc;
-    {
-        int cnt = 0;
-        if (hipGetDeviceCount(&cnt) != hipSuccess || device >= cnt) return HALO_E_NODEV;
-    }
+    if ((rc = halo::device_present(device))) return rc;
     halo::DeviceScope ds(device);
     if ((rc = halo::check_device())) return rc;
     halo::ParkResidents park(device);  // the drains, table growth (hipFree) and copies below

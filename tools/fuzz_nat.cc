@@ -3,7 +3,8 @@
 // calls through the public C ABI — add, both gets, port mappings, the miss slow path, expire,
 // list with a short cap, layout statistics at automatic and forced capacity — over a small key
 // universe (so keys are replaced, ports run out of order and allocators empty) and checks the
-// invariants a caller relies on. tests/test_sanitize_nat.py builds and runs it.
+// invariants a caller relies on, then that the sync and every device lookup of this host-only
+// build answer HALO_E_NODEV. tests/test_sanitize_nat.py builds and runs it.
 //
 //   g++ -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -Ihalo_amd/csrc
 //       halo_amd/csrc/nat_table.cc tools/fuzz_nat.cc -o fuzz_nat && ./fuzz_nat 300000 0x5EED
@@ -156,6 +157,17 @@ int main(int argc, char** argv) {
             }
         }
     }
+    // this build has no device side
+    CHECK(halo_nat_sync_device(tabs[0], 0) == HALO_E_NODEV);
+    CHECK(halo_nat_sync_device(tabs[0], -1) == HALO_E_INVAL && halo_nat_sync_device(nullptr, 0) == HALO_E_INVAL);
+    CHECK(halo_nat_lookup_wan_device(tabs[0], nullptr, 0, now, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == HALO_E_NODEV);
+    CHECK(halo_nat_lookup_lan_device(tabs[0], nullptr, 0, now, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == HALO_E_NODEV);
+    CHECK(halo_nat_lookup_wan_compact_device(tabs[0], nullptr, 0, now, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) ==
+          HALO_E_NODEV);
+    CHECK(halo_nat_lookup_lan_compact_device(tabs[0], nullptr, 0, now, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) ==
+          HALO_E_NODEV);
+    CHECK(halo_nat_lookup_quote_device(tabs[0], nullptr, 0, nullptr, nullptr) == HALO_E_NODEV);
+    CHECK(halo_nat_lookup_wan_device(nullptr, nullptr, 0, now, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == HALO_E_INVAL);
     for (auto* t : tabs) CHECK(halo_nat_table_destroy(t) == HALO_OK);
     CHECK(halo_nat_table_destroy(nullptr) == HALO_E_INVAL);
     printf("nat fuzz: %ld calls, %lu flows added, %lu nil, %lu get hits, %lu removed, %lu resolves, %lu lists, %lu range\n",
