@@ -57,6 +57,19 @@ static inline halo_kcp_config_t gpurx_kcp_config(int byte_check_mode, uint32_t p
     return c;
 }
 
+// gpurx_kcp_emit_config: a halo_kcp_emit_config_t (byte_check_mode is HALO_KCP_CHECK_*, -1..2).
+static inline halo_kcp_emit_config_t gpurx_kcp_emit_config(int byte_check_mode, uint32_t src_ip, uint32_t src_port,
+                                                           uint32_t dgram_cap, uint32_t stream_cap) {
+    halo_kcp_emit_config_t c;
+    c.byte_check_mode = byte_check_mode;
+    c.src_ip = src_ip;
+    c.src_port = src_port;
+    c.dgram_cap = dgram_cap;
+    c.stream_cap = stream_cap;
+    c.reserved = 0;
+    return c;
+}
+
 // gpurx_parse_one: one frame (l3 = 0) or one bare IPv4 packet (l3 = 1) through the host entry
 // point, as a batch of one. The netif only sets the dispatch flags, which the Parse* wrappers
 // do not read.

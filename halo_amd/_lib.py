@@ -194,6 +194,19 @@ KCP_CHECK_MODES = {"disabled": -1, "zero": 0, "crc32": 1, "xxh3": 2}  # byte_che
 KCP_DGRAM_KCP, KCP_DGRAM_ENET = 0, 1
 KCP_ENET_NAMES = ("ConnEnetSyn", "ConnEnetEst", "ConnEnetFin", "ConnEnetPing")  # conn_type
 KCP_SEG_CHECK_NA, KCP_SEG_CHECK_PASSED, KCP_SEG_CHECK_FAILED = 0, 1, 2
+# KCP emit: halo_kcp_out_session_t (40 bytes), halo_kcp_out_dgram_t (16), halo_kcp_emit_summary_t (88), HALO_KCP_EMIT_*
+KCP_OUT_SESSION_DTYPE = np.dtype([("conv", "<u8"), ("first_seg", "<u4"), ("n_segs", "<u4"), ("dst_ip", "<u4"), ("dst_port", "<u2"),
+                                  ("mtu", "<u2"), ("kind", "u1"), ("conn_type", "u1"), ("reserved", "<u2"), ("session_id", "<u4"),
+                                  ("enet_conv", "<u4"), ("enet_type", "<u4")])
+KCP_OUT_DGRAM_DTYPE = np.dtype([("offset", "<u4"), ("len", "<u2"), ("n_segs", "<u2"), ("session", "<u4"), ("first_seg", "<u4")])
+KCP_EMIT_SUMMARY_DTYPE = np.dtype([("sessions", "<u4"), ("sessions_written", "<u4"), ("dgrams", "<u4"), ("dgrams_written", "<u4"),
+                                   ("segs", "<u4"), ("segs_written", "<u4"), ("status_counts", "<u4", (4,)), ("bytes", "<u8"),
+                                   ("bytes_written", "<u8"), ("bytes_hashed", "<u8"), ("out_segs", "<u8"), ("out_pkts", "<u8"),
+                                   ("out_bytes", "<u8")])
+assert (KCP_OUT_SESSION_DTYPE.itemsize, KCP_OUT_DGRAM_DTYPE.itemsize, KCP_EMIT_SUMMARY_DTYPE.itemsize) == (40, 16, 88)
+KCP_EMIT_STATUS_NAMES = ("OK", "SEG_TOO_LONG", "BAD_MTU", "BAD_RANGE")
+KCP_EMIT_STATUS = {name: code for code, name in enumerate(KCP_EMIT_STATUS_NAMES)}
+KCP_EMIT_MAX = 1 << 23
 # halo_rx_ring_scan_t (24 bytes) and HALO_RING_STOP_* / HALO_RING_REGISTER
 RING_SCAN_DTYPE = np.dtype([("n_frames", "<u4"), ("stop", "<u4"), ("end_bytes", "<u8"), ("max_len", "<u4"),
                             ("pad", "<u4")])
@@ -357,6 +370,16 @@ class KcpConfig(ctypes.Structure):
 
 
 assert ctypes.sizeof(KcpConfig) == 16
+
+
+class KcpEmitConfig(ctypes.Structure):
+    """halo_kcp_emit_config_t."""
+
+    _fields_ = [("byte_check_mode", ctypes.c_int32), ("src_ip", ctypes.c_uint32), ("src_port", ctypes.c_uint32),
+                ("dgram_cap", ctypes.c_uint32), ("stream_cap", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(KcpEmitConfig) == 24
 
 
 class BatchDesc(ctypes.Structure):
@@ -573,6 +596,12 @@ _PROTOS = {
     "halo_kcp_ingest_device": (ctypes.c_int, [
         ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64, ctypes.c_void_p]),
     "halo_kcp_ingest_host": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p]),
+    "halo_kcp_emit_workspace": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    "halo_kcp_emit_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p, _u8p,
+        _u8p, ctypes.c_uint64, ctypes.c_void_p]),
+    "halo_kcp_emit_host": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p, _u8p]),
     "halo_synth_layout": (ctypes.c_int, [
         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint64)]),

@@ -16,7 +16,7 @@
 //           atomic per non-zero counter into the summary.
 //   hash    CRC32: crc_kernel, a group of kCrcLanes lanes per PUSH descriptor, each lane a
 //           contiguous kCrcChunk-byte chunk read as whole aligned dwords (rx_kcp.h says how chunks
-//           combine). The chunk CRC is shift/xor arithmetic, 32 steps per dword, not LDS slice
+//           combine; the group's code is kcp_crc_device.h's, shared with tx_kcp.hip). The chunk CRC is shift/xor arithmetic, 32 steps per dword, not LDS slice
 //           tables: the lanes of a wave index a table with unrelated bytes, so a 64-bank LDS serves
 //           such a wave-wide lookup in several conflict passes, four lookups per dword, and every
 //           workgroup would first have to build 4 KiB of tables; the arithmetic needs no memory at
@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include "halo_common.h"
+#include "kcp_crc_device.h"
 #include "rx_kcp.h"
 #include "tile_scan.h"
 
@@ -213,37 +214,6 @@ uint32_t hash_grid(uint64_t items, uint32_t per) {
     return (uint32_t)(b > cap ? cap : (b ? b : 1));
 }
 
-// `n` (1..4) data bytes at stream byte address a, in the low bytes
-__device__ __forceinline__ uint32_t data_bytes(const uint32_t* dw, uint32_t a, uint32_t n) {
-    const uint32_t s = a & 3u, lo = dw[a >> 2], hi = s + n > 4u ? dw[(a >> 2) + 1] : 0u;
-    return deliver::funnel(lo, hi, s) & (n == 4u ? 0xFFFFFFFFu : (1u << 8u * n) - 1u);
-}
-
-// The CRC register after data bytes [b0, b1) at stream address a + b0.., from register c.
-__device__ __forceinline__ uint32_t crc_chunk(const uint32_t* dw, uint32_t a, uint32_t b0, uint32_t b1, uint32_t c) {
-    const uint32_t head = (b1 - b0) & 3u;  // a partial dword first: the rest ends on the chunk's end
-    if (head) {
-        c = kcp::crc_steps(c ^ data_bytes(dw, a + b0, head), 8u * head);
-        b0 += head;
-    }
-    const uint32_t n = (b1 - b0) >> 2;
-    if (n == 0) return c;
-    const uint32_t at = a + b0, s = at & 3u;
-    const uint32_t* p = dw + (at >> 2);
-    uint32_t cur = p[0];
-    for (uint32_t i = 0; i < n; ++i) {
-        uint32_t w = cur;
-        if (s) {  // the dword's last s bytes lie in the next word
-            cur = p[i + 1];
-            w = deliver::funnel(w, cur, s);
-        } else if (i + 1 < n) {
-            cur = p[i + 1];
-        }
-        c = kcp::crc_steps(c ^ w, 32);
-    }
-    return c;
-}
-
 __global__ void __launch_bounds__(kHashBlock) kcp_crc_kernel(const KcpParams q) {
     const uint32_t written = q.summary->segs_written;
     const uint32_t g = threadIdx.x % kcp::kCrcLanes;
@@ -251,29 +221,9 @@ __global__ void __launch_bounds__(kHashBlock) kcp_crc_kernel(const KcpParams q) 
     for (uint32_t s = blockIdx.x * per + threadIdx.x / kcp::kCrcLanes; s < written; s += gridDim.x * per) {  // group-uniform
         const uint4 lo = q.segs[2ull * s], hi = q.segs[2ull * s + 1];
         if ((lo.y & 0xFFu) != kcp::kCmdPush) continue;
-        const uint32_t len = hi.y, a = hi.z, P = kcp::crc_passes(len);
-        uint32_t v = 0;
-        for (uint32_t p = 0; p < P; ++p) {
-            uint32_t b0, b1;
-            bool first;
-            kcp::crc_lane_range(len, P, p, g, &b0, &b1, &first);
-            if (p) v = kcp::crc_mulmod(v, kcp::kCrcXStride);  // pass 0 starts from zero
-            if (b1 > b0) v ^= crc_chunk(q.stream, a, b0, b1, first ? 0xFFFFFFFFu : 0u);
-        }
-        // level l: lane g of every 2^(l+1) takes in lane g + 2^l. A one-pass segment occupies only its
-        // last `occ` lanes: while occ <= 2^l the receiving lanes still hold zero, and zero times a
-        // power of x is zero, so the multiplication is skipped (group-uniform).
-        constexpr uint32_t x0 = kcp::crc_xlevel(0), x1 = kcp::crc_xlevel(1), x2 = kcp::crc_xlevel(2), x3 = kcp::crc_xlevel(3);
-        static_assert(kcp::kCrcLevels == 4, "four levels written out");
-        const uint32_t occ = P > 1 ? kcp::kCrcLanes : (len + kcp::kCrcChunk - 1) / kcp::kCrcChunk;
-        v = (occ > 1 ? kcp::crc_mulmod(v, x0) : v) ^ __shfl_down(v, 1, kcp::kCrcLanes);
-        v = (occ > 2 ? kcp::crc_mulmod(v, x1) : v) ^ __shfl_down(v, 2, kcp::kCrcLanes);
-        v = (occ > 4 ? kcp::crc_mulmod(v, x2) : v) ^ __shfl_down(v, 4, kcp::kCrcLanes);
-        v = (occ > 8 ? kcp::crc_mulmod(v, x3) : v) ^ __shfl_down(v, 8, kcp::kCrcLanes);
-        if (g == 0) {
-            const uint32_t crc = len ? ~v : 0u;
+        const uint32_t crc = crc_group(q.stream, hi.z, hi.y, g);
+        if (g == 0)
             reinterpret_cast<uint32_t*>(q.segs)[8ull * s + 7] = crc == q.want[s] ? HALO_KCP_SEG_CHECK_PASSED : HALO_KCP_SEG_CHECK_FAILED;
-        }
     }
 }
 

@@ -1761,7 +1761,8 @@ HALO_API int halo_rx_deliver_host(const halo_deliver_config_t* cfg, const uint8_
  * dgrams, index, both summaries, workspace: 8; stream: 4) or workspace_bytes <
  * halo_kcp_ingest_workspace(index_cap, seg_cap). index_cap == 0, or an empty delivery, zeroes the
  * summary. A build without HIP answers HALO_E_NODEV.
- * Not covered: sessions, ARQ (parse_ack / parse_data / flush), the ENet handshake, FEC, transmit. */
+ * Not covered: sessions, ARQ (parse_ack / parse_data / flush's decisions), the ENet handshake, FEC.
+ * Transmit: "KCP emit" below. */
 #define HALO_KCP_CHECK_DISABLED (-1)
 #define HALO_KCP_CHECK_ZERO 0
 #define HALO_KCP_CHECK_CRC32 1
@@ -1835,6 +1836,135 @@ HALO_API int halo_kcp_ingest_host(const halo_kcp_config_t* cfg, const uint8_t* s
                                   const halo_deliver_summary_t* deliver_summary, const halo_deliver_index_t* index,
                                   uint32_t index_cap, halo_kcp_dgram_t* dgrams, halo_kcp_seg_t* segs,
                                   halo_kcp_summary_t* summary);
+
+/* ---- KCP emit: pack, encode and byte-check a flush batch ---------------------------------------
+ * The stateless tail of the reference's KCP transmit path, for payload that lies in HBM: what
+ * KCP.flush (protocol/kcp/kcp.go:770-950) does to bytes once the session has decided what to send —
+ * makeSpace / flushBuffer's greedy packing of segments into datagrams of at most mtu bytes,
+ * segment.encode (kcp.go:134-155) with byte_check_hash(data) for every PUSH, the copy of the data —
+ * and the listener's BuildEnet control packets (enet.go:75-97). The state machine (which segments,
+ * ts / wnd / una / sn, RTO, cwnd, the ack list) stays with the host, which works from descriptors
+ * only. The output is ready for halo_tx_build_batch_device with d_payload = d_stream.
+ * INPUT
+ *   halo_kcp_out_session_t [n_sessions], in the caller's order: one flush (KCP) or one control
+ *     packet (ENET) each. Every entry's [first_seg, first_seg + n_segs) must lie in the segment list
+ *     and start at or behind the previous ENTRY's end (entry s is held against entry s - 1 alone,
+ *     whatever that one's status): ascending and disjoint, gaps allowed. An ENET entry has n_segs 0
+ *     and any first_seg that keeps the order.
+ *   halo_kcp_seg_t [n_segs]: the descriptor KCP ingest writes, so a relay hands ingest's output
+ *     back. Used: cmd, frg, wnd, ts, sn, una, len, and data_off = the byte offset of the data in
+ *     d_payload, at any alignment. dgram and check are ignored.
+ *   d_payload [payload_bytes].
+ *   cfg: byte_check_mode as in ingest (H = 28 when disabled, else 32), src_ip / src_port (the served
+ *     port) for the descriptors, dgram_cap, stream_cap (bytes).
+ * A KCP session (flush with reserved == 0: sess.headerSize is never set in the reference): size = 0;
+ *   for each segment in order need = H + len; if size + need > mtu the datagram ends and size = 0;
+ *   size += need; at the end a non-empty datagram is output. No segments, no datagram. The ack
+ *   entries flush filters out are simply not in the list, and a makeSpace call that no encode
+ *   follows changes nothing, so the packing is flush's. A segment (encode): conv u64, cmd, frg, wnd
+ *   u16, ts, sn, una, len u32, and with H == 32 a u32 that is byte_check_hash(data) for cmd 81 in
+ *   CRC32 / XXH3 mode and 0 otherwise; then len data bytes, for any cmd (cmd is not validated:
+ *   encode does not).
+ * An ENET entry: one 20-byte datagram, BuildEnet(conn_type, enet_type, session_id, enet_conv).
+ * STATUS per entry, the first that applies:
+ *   BAD_RANGE     first_seg + n_segs > n_segs; first_seg before the previous entry's end (so the
+ *                 entry behind one whose range ends past the list is BAD_RANGE too); ENET with
+ *                 conn_type > 3 or n_segs != 0; a kind that is neither
+ *   BAD_MTU       KCP: mtu <= H or mtu > 1472 (BuildUdpPkt's limit)
+ *   then per segment in order, the first that fails:
+ *   BAD_RANGE     [data_off, data_off + len) not inside payload_bytes
+ *   SEG_TOO_LONG  H + len > mtu (Go would index past kcp.buffer; Send never makes one)
+ *   A non-OK entry emits nothing and does not end the written prefix.
+ * OUTPUT, all little-endian, all SET (nothing is cleared beforehand)
+ *   d_status [n_sessions], HALO_KCP_EMIT_*.
+ *   d_stream [stream_cap]: the datagrams of the OK entries in order, each at a multiple of 4, pad
+ *     bytes zero (also behind the last), so the stream is deterministic over [0, bytes_written).
+ *   halo_kcp_out_dgram_t [dgram_cap] and halo_tx_build_desc_t [dgram_cap], one of each per
+ *     datagram: payload_off / payload_len the datagram's, proto 17, src from cfg, dst from the
+ *     entry, mode HALO_TX_BUILD_ETH, everything else zero (halo_arp_encap_tx_device fills the MAC).
+ *   halo_kcp_emit_summary_t: sessions / dgrams / segs / bytes and status_counts are totals over the
+ *     whole call (sessions counts the OK entries; bytes the stream bytes with padding); the other
+ *     counters describe the written prefix.
+ * CAPACITY (the egress rule): an OK entry's datagrams are written while all of them fit dgram_cap
+ *   and stream_cap; the first OK entry that does not fit ends the written prefix. Totals stay
+ *   totals. Ranges of OK entries can overlap only across a non-OK entry between them; they are then
+ *   emitted as given, segs_written is held to n_segs as a third capacity, and the u32 totals are
+ *   exact while they fit (disjoint ranges always do).
+ * READS: the session and segment arrays; data only as aligned 4-byte words that hold data bytes of
+ *   in-range segments. WRITES: exactly the written prefixes, all of d_status and the summary.
+ * The device call is asynchronous on `stream` with no host round trip. Arguments are checked before
+ * any device call. HALO_E_INVAL: a null cfg or summary; byte_check_mode outside -1..2; src_port
+ * above 65535; n_sessions or n_segs above HALO_KCP_EMIT_MAX; a null sessions / status with
+ * n_sessions > 0, segs with n_segs > 0, payload with payload_bytes > 0, dgrams / descs with
+ * dgram_cap > 0, stream with stream_cap > 0; for the device call a misaligned array (segs, dgrams:
+ * 16; sessions, descs, summary, workspace: 8; payload, stream: 4) or workspace_bytes <
+ * halo_kcp_emit_workspace(n_sessions, n_segs). n_sessions == 0 zeroes the summary. A build without
+ * HIP answers HALO_E_NODEV.
+ * Not covered: SetDUP duplication, ReserveBytes, sessions, ARQ and the ENet state machine. */
+#define HALO_KCP_EMIT_OK 0u
+#define HALO_KCP_EMIT_SEG_TOO_LONG 1u
+#define HALO_KCP_EMIT_BAD_MTU 2u
+#define HALO_KCP_EMIT_BAD_RANGE 3u
+#define HALO_KCP_EMIT_MAX (1u << 23) /* entries and segments per call: every total fits a u32 */
+typedef struct halo_kcp_emit_config {
+    int32_t byte_check_mode; /* HALO_KCP_CHECK_*                                       */
+    uint32_t src_ip;         /* the descriptors' source                                */
+    uint32_t src_port;       /* the served UDP port                                    */
+    uint32_t dgram_cap;      /* entries in dgrams and descs                            */
+    uint32_t stream_cap;     /* bytes in stream                                        */
+    uint32_t reserved;       /* 0                                                      */
+} halo_kcp_emit_config_t;    /* 24 B */
+typedef struct halo_kcp_out_session {
+    uint64_t conv;       /* KCP: kcp.conv                                              */
+    uint32_t first_seg;  /* its range in the segment list                              */
+    uint32_t n_segs;
+    uint32_t dst_ip;     /* s.remote                                                   */
+    uint16_t dst_port;
+    uint16_t mtu;        /* KCP: kcp.mtu                                               */
+    uint8_t kind;        /* HALO_KCP_DGRAM_KCP / _ENET                                 */
+    uint8_t conn_type;   /* ENET: HALO_KCP_ENET_*                                      */
+    uint16_t reserved;   /* 0                                                          */
+    uint32_t session_id; /* ENET: BuildEnet's sessionId, conv and enetType             */
+    uint32_t enet_conv;
+    uint32_t enet_type;
+} halo_kcp_out_session_t; /* 40 B */
+typedef struct halo_kcp_out_dgram {
+    uint32_t offset;    /* of the datagram in the stream, a multiple of 4              */
+    uint16_t len;       /* its bytes                                                   */
+    uint16_t n_segs;    /* segments in it (ENET: 0)                                    */
+    uint32_t session;   /* the entry it belongs to                                     */
+    uint32_t first_seg; /* its first segment's index in the segment list               */
+} halo_kcp_out_dgram_t; /* 16 B */
+typedef struct halo_kcp_emit_summary { /* SET by the call */
+    uint32_t sessions;         /* OK entries, also beyond the capacities               */
+    uint32_t sessions_written; /* those of the written prefix                          */
+    uint32_t dgrams;
+    uint32_t dgrams_written;
+    uint32_t segs;             /* segments of the OK entries                           */
+    uint32_t segs_written;
+    uint32_t status_counts[4]; /* entries per HALO_KCP_EMIT_*                          */
+    uint64_t bytes;            /* stream bytes, padding included                       */
+    uint64_t bytes_written;
+    uint64_t bytes_hashed;     /* CRC32 / XXH3: data bytes of the written PUSH segments */
+    uint64_t out_segs;         /* DefaultSnmp.OutSegs (one per encode, kcp.go:153) and  */
+    uint64_t out_pkts;         /* OutPkts / OutBytes as defaultTx adds them with dup == */
+    uint64_t out_bytes;        /* 0 (udp_socket.go:60-82), for the written datagrams    */
+} halo_kcp_emit_summary_t;     /* 88 B */
+/* Bytes of device workspace (8-byte aligned, no initialisation). One workspace serves any number
+ * of calls issued on one stream. */
+HALO_API uint64_t halo_kcp_emit_workspace(uint32_t n_sessions, uint32_t n_segs);
+HALO_API int halo_kcp_emit_device(const halo_kcp_emit_config_t* cfg, const halo_kcp_out_session_t* d_sessions,
+                                  uint32_t n_sessions, const halo_kcp_seg_t* d_segs, uint32_t n_segs,
+                                  const uint8_t* d_payload, uint64_t payload_bytes, uint8_t* d_stream,
+                                  halo_kcp_out_dgram_t* d_dgrams, halo_tx_build_desc_t* d_descs, uint8_t* d_status,
+                                  halo_kcp_emit_summary_t* d_summary, void* d_workspace, uint64_t workspace_bytes,
+                                  halo_stream_t stream);
+/* The same outputs from the sequential loop over host memory; no HIP. Picked by name, never a
+ * fallback. Arrays need no alignment. */
+HALO_API int halo_kcp_emit_host(const halo_kcp_emit_config_t* cfg, const halo_kcp_out_session_t* sessions,
+                                uint32_t n_sessions, const halo_kcp_seg_t* segs, uint32_t n_segs, const uint8_t* payload,
+                                uint64_t payload_bytes, uint8_t* stream, halo_kcp_out_dgram_t* dgrams,
+                                halo_tx_build_desc_t* descs, uint8_t* status, halo_kcp_emit_summary_t* summary);
 
 /* ---- synthetic traffic (bench + tests; SURVEY.md §8d generator) ----------------------
  * Every field of frame i is a pure function of (seed, i), so any shard of the global
