@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "halo_amd", "csrc")
 OUT = os.path.join(ROOT, "halo_amd", "lib", "libhalo_rx.so")
-SOURCES = ["rx_parse.hip", "tx_fixup.hip", "tx_build.hip", "deep_nat.hip", "flow_hash.hip", "route_lpm.hip", "synth.hip", "host_path.hip",
+SOURCES = ["rx_lane.hip", "rx_group.hip", "rx_stream.hip", "rx_parse.hip", "rx_hist.hip", "tx_fixup.hip", "tx_build.hip", "deep_nat.hip", "flow_hash.hip", "route_lpm.hip", "synth.hip", "host_path.hip",
            "ring_rx.hip", "resident.hip", "host_logic.cc", "nat_lookup.hip", "nat_table.cc", "switch_fwd.hip", "switch_table.cc",
            "arp_fwd.hip", "arp_table.cc", "tx_egress.hip", "tx_egress_host.cc", "tx_respond.hip", "tx_respond_host.cc",
            "pmflow_fwd.hip", "pmflow_table.cc", "tx_ring.hip", "tx_ring_host.cc", "rx_deliver.hip", "rx_deliver_host.cc",
@@ -23,7 +23,7 @@ BENCH_OUT = os.path.join(ROOT, "tools", "libhalo_bench.so")
 CPU_SRC = os.path.join(CSRC, "rx_cpu.cc")
 CPU_OUT = os.path.join(ROOT, "halo_amd", "lib", "libhalo_rx_cpu.so")
 HEADERS = ["halo_common.h", "halo_limits.h", "host_logic.h", "device_util.h", "flow_key.h", "flow_table.h", "nat_table.h", "switch_table.h", "arp_table.h", "tx_egress.h",
-           "tx_respond.h", "tx_ring.h", "rx_deliver.h", "rx_kcp.h", "tx_kcp.h", "kcp_check_host.h", "kcp_crc_device.h", "pmflow_table.h", "rx_dispatch.h", "route_view.h", "tile_scan.h", "stream_scan.h", "host_layout.h", "device_table.h", os.path.join("..", "..", "include", "halo_rx.h")]
+           "tx_respond.h", "tx_ring.h", "rx_deliver.h", "rx_kcp.h", "tx_kcp.h", "kcp_check_host.h", "kcp_crc_device.h", "pmflow_table.h", "rx_dispatch.h", "route_view.h", "tile_scan.h", "stream_scan.h", "rx_frame.h", "rx_hist.h", "rx_launch.h", "host_layout.h", "device_table.h", os.path.join("..", "..", "include", "halo_rx.h")]
 
 
 def _hipcc() -> str:

@@ -13,7 +13,7 @@
 // one 64-lane wave per frame, the frame staged in the wave's LDS region, header logic evaluated
 // redundantly by every lane (uniform), byte edits by lane 0, and each GetCheckSum a wave-parallel
 // sum of the LDS dwords of its region in the little-endian domain (every region starts at an
-// even frame offset: 34, 42, 62), as rx_parse.hip.
+// even frame offset: 34, 42, 62), as rx_frame.h.
 #include <hip/hip_runtime.h>
 
 #include "device_util.h"

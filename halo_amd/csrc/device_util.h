@@ -1,4 +1,4 @@
-// device_util.h — wave-level building blocks shared by the gfx950 kernels (rx_parse.hip,
+// device_util.h — wave-level building blocks shared by the gfx950 kernels (rx_frame.h,
 // tx_fixup.hip): one's-complement folds, group broadcast / reduction over DPP, and the
 // global-address-space 16-byte frame load. gfx950 (CDNA4, wave64) only.
 #pragma once
@@ -60,7 +60,7 @@ __device__ __forceinline__ uint32_t group_sum(uint32_t x) {
 typedef const __attribute__((address_space(1))) uint32_t gu32;
 
 // load4 with a non-temporal hint on the 16-byte path (bytes read once: not kept in the L2 ahead
-// of lines another group will read). Only the 16-lane groups' later rounds take it (rx_parse.hip,
+// of lines another group will read). Only the 16-lane groups' later rounds take it (rx_frame.h,
 // kLaterNtG); tried: every load4 non-temporal (in git history up to 9ac2a89).
 __device__ __forceinline__ void load4_nt(const uint8_t* frame, uint32_t d0, uint32_t ndw, uint32_t (&w)[4]) {
     gu32* p = (gu32*)(reinterpret_cast<const uint32_t*>(frame) + d0);

@@ -1,5 +1,5 @@
 // flow_key.h — the NAT flow key of a parsed record and its XXH3-64, shared
-// by the standalone flow-hash kernel (flow_hash.hip) and the rx kernels' fused pass (rx_parse.hip,
+// by the standalone flow-hash kernel (flow_hash.hip) and the rx kernels' fused pass (rx_frame.h,
 // halo_rx_parse_flow_batch_device), so the two produce the same bits by construction.
 //
 //   key (13 bytes, little-endian): remote ip u32 | remote port u16 | local ip u32 | local port u16

@@ -61,7 +61,7 @@ enum SynthSlot : uint32_t {
 
 int check_device();  // 0 if the current device is gfx950, else HALO_E_*
 
-// Partial status histograms of an rx launch (flush_hist, rx_parse.hip). A tree is kHistSlots
+// Partial status histograms of an rx launch (flush_hist, rx_hist.h). A tree is kHistSlots
 // level-1 slots (one per block modulo kHistSlots) then kHistSlots / kHistFan level-2 slots,
 // kHistStride 64-bit words each (arrivals << 40 | count, one per status), zero between launches.
 // Trees belong to HSA queues, not to streams: a device's tree set holds kHistTrees trees and a key
@@ -95,7 +95,7 @@ int hist_trees_reset_keys(int device);
 int hist_keys_debug(int device, int op, uint32_t arg);
 
 // The resident small-poll consumer of a ring attached with HALO_RING_PERSISTENT (ring_rx.hip
-// drives it, rx_parse.hip runs it): kSvcGroups workgroups that wait on this control block, in
+// drives it, rx_lane.hip runs it): kSvcGroups workgroups that wait on this control block, in
 // pinned host memory, for a request, parse its n frames as the lane kernel would (frames at
 // data + 4 * off_dw[i], the host's ReadPacket walk wrote off_dw / lens into pinned memory; 64-frame
 // windows dealt round-robin over the groups) and write their records to `out`; each group then

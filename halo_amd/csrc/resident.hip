@@ -1,4 +1,4 @@
-// resident.hip — the host side of the resident consumer (rx_parse.hip ring_service_kernel): one
+// resident.hip — the host side of the resident consumer (rx_lane.hip ring_service_kernel): one
 // control block in pinned coherent memory, one kernel that stays on kSvcGroups CUs while requests
 // keep coming, and the registry that lets a device drain stop every consumer first.
 //

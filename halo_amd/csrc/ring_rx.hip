@@ -6,7 +6,7 @@
 // (dpdk.EthQueueRxPkt, dpdk/dpdk.go:183-199; engine.Wire.Rx, engine/engine.go:535-545) and
 // PacketHandle parses it (engine/engine.go:339-351). Here a consumer takes everything between its
 // cursor and the producer's head in one poll: the span goes to HBM raw (one DMA, two around the
-// wrap), the GPU finds the record boundaries, the rx kernel (rx_parse.hip) parses the frames where
+// wrap), the GPU finds the record boundaries, the rx kernel (rx_parse.hip picks it) parses the frames where
 // they lie, and the records come back in one copy. The host reads `head`, writes `tail`, and never
 // touches a frame byte.
 //
@@ -695,7 +695,7 @@ struct halo_rx_ring {
     uint32_t* d_soff = nullptr;
     uint16_t* d_slen = nullptr;
     halo_rx_result_t* d_sres = nullptr;
-    // HALO_RING_PERSISTENT: the resident small-poll consumer (resident.hip, rx_parse.hip
+    // HALO_RING_PERSISTENT: the resident small-poll consumer (resident.hip, rx_lane.hip
     // ring_service_kernel) over the ring's data area and the pinned offset / length arrays
     halo::Resident* svc = nullptr;
     halo_rx_ring_stats_t stats{};

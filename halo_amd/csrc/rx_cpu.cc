@@ -3,7 +3,7 @@
 // the explicit CPU entry point of SURVEY.md §8b for polls too small to pay a GPU round trip, not a
 // fallback for a missing device.
 //
-// Per frame, in reference order (the same verdicts and record fields as rx_parse.hip's
+// Per frame, in reference order (the same verdicts and record fields as rx_frame.h's
 // parse_header / finish_l4 / frame_store):
 //   ParseEthFrm        protocol/ethernet.go:29-55   length caps, EtherType whitelist
 //   RxEthernet filter  engine/ethernet_engine.go:22 dst MAC == own || broadcast
@@ -218,7 +218,7 @@ inline void parse_one(const uint8_t* f, uint32_t L, const Own& own, halo_rx_resu
 }
 
 // The 16-byte record of a full one (HALO_RX_RECORD_COMPACT, include/halo_rx.h): the EtherType as
-// its class in flags bits 4-5, as rx_parse.hip's frame_store packs it.
+// its class in flags bits 4-5, as rx_frame.h's frame_store packs it.
 inline halo_rx_record16_t compact(const halo_rx_result_t& r) {
     halo_rx_record16_t c;
     const uint32_t et_class = r.ethertype == kEthArp ? HALO_RX_F_ET_ARP

@@ -26,7 +26,7 @@
 // memory round trip, each dword = header bytes | payload bytes (two aligned source loads merged
 // with v_alignbyte: the payload may start at any byte) | zero padding. The L4 checksum is summed
 // over the output dwords as they are produced (v_dot2_u32_u16 of each dword's halves: the
-// one's-complement sum in the little-endian domain, as rx_parse.hip; the L4 segment starts at an
+// one's-complement sum in the little-endian domain, as rx_frame.h; the L4 segment starts at an
 // even frame offset), reduced over the group with DPP, and patched into the header chunks, which
 // are stored last. Chunks wholly inside the payload skip every mask; a lane-per-frame frame of
 // <= 64 B is built whole in registers with no per-dword branch (build_small), staged in LDS and

@@ -9,13 +9,13 @@
 //                                  rte_ipv4_udptcp_cksum, restated in oracle/halo_tx_oracle.c)
 // in the order Ipv4RouteForward applies them (engine/ipv4_engine.go:108-269).
 //
-// Shape: the rx kernel's (rx_parse.hip) — G lanes of a wave per frame, 16-byte loads, header
+// Shape: the rx kernel's (rx_frame.h) — G lanes of a wave per frame, 16-byte loads, header
 // dwords 0..12 broadcast to the group. Every step only rewrites header bytes (< 52), and every
 // checksum the steps ask for is a function of the FINAL packet bytes (no checksum field lies in
 // another checksum's range), so the steps are first applied to a register copy of the header,
 // then each needed checksum is summed once over the final bytes: header dwords from the copy,
 // the rest of the frame from the loads. Sums are taken in the little-endian dword domain (see
-// rx_parse.hip): the stored field, read as a little-endian half-word, is ~fold(sum) — for the
+// rx_frame.h): the stored field, read as a little-endian half-word, is ~fold(sum) — for the
 // Go functions (big-endian store of ^fold(BE sum)) and for DPDK (host-order store of
 // ~rte_raw_cksum) alike. One lane per frame then writes the dirty header dwords back.
 #include <hip/hip_runtime.h>

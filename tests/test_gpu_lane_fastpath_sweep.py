@@ -75,7 +75,7 @@ def bit_sweep():
 
 
 def is_plain(rows, lens):
-    """The fast path's predicate restated (rx_parse.hip, lane_plain and the length ballot), one
+    """The fast path's predicate restated (rx_lane.hip, lane_plain and the length ballot), one
     bool per row. Asserted as a population only; never an expected value."""
     tl = rows[:, 16].astype(np.int64) << 8 | rows[:, 17]
     return ((lens >= 61) & (lens <= 64)

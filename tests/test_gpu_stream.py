@@ -1,4 +1,4 @@
-"""GPU: the byte-stream kernel (HALO_RX_VARIANT_STREAM, rx_parse.hip rx_stream_kernel) on the
+"""GPU: the byte-stream kernel (HALO_RX_VARIANT_STREAM, rx_stream.hip rx_stream_kernel) on the
 layouts its window logic distinguishes, every record bit-exact against the C oracle:
 dense in index order (one coalesced pass per window), frames shuffled inside their window
 (out-of-order segments, still dense), frames shuffled across the whole buffer and frames with

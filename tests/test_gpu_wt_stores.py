@@ -1,5 +1,5 @@
 """GPU: the lane kernel's staged, masked record stores under any store policy (plain, non-temporal
-or write-through: store16 in rx_parse.hip) — bit-exact records vs the C oracle at
+or write-through: store16 in rx_frame.h) — bit-exact records vs the C oracle at
 the window edges, at every alignment of ``out``, across dependent launches into one ``out``, as
 seen by every kind of consumer, in looping waves and through the other entry points that share
 the window code. Nothing here depends on which policy the library was built with: a policy may

@@ -1,4 +1,4 @@
-"""CPU: the status histogram's trees (rx_parse.hip flush_hist), restated in Python: the two-level tree
+"""CPU: the status histogram's trees (rx_hist.h flush_hist), restated in Python: the two-level tree
 (grids above 16384 blocks) and, at the end of the file, the one level of 16-block runs.
 
 Every block adds (1 << 40 | count) to status word k of level-1 slot b % 1024; the add that brings
@@ -57,7 +57,7 @@ def test_tree_counts_exact_and_words_reset(g):
         assert all(v == 0 for v in l1.values()) and all(v == 0 for v in l2.values())
 
 
-RUN = 16  # kHistRuns (rx_parse.hip, flush_hist)
+RUN = 16  # kHistRuns (rx_hist.h, flush_hist)
 
 
 def run_runs(counts: np.ndarray, order: np.ndarray, words: dict, out: np.ndarray) -> int:
