@@ -1,7 +1,8 @@
 // rx_lane.hip — the lane-per-frame rx kernels: a wave's window of 64 consecutive frames, a lane each
 // (lane_window: the straight-line fast path for windows of plain frames, frame_finish otherwise),
-// run by rx_lane_kernel, its lean instance for launches without a histogram, the several-batches
-// kernel, and the resident small-poll consumer (ring_service_kernel); and their launches.
+// run by rx_lane_kernel, its lean instance for launches without a histogram (rx_lane_lean1_kernel,
+// one window per wave and no loop, when the grid covers the batch; rx_lane_lean_kernel otherwise), the
+// several-batches kernel, and the resident small-poll consumer (ring_service_kernel); and their launches.
 // The per-frame code is rx_frame.h, the histogram rx_hist.h.
 #include <hip/hip_runtime.h>
 
@@ -192,6 +193,18 @@ __device__ __forceinline__ void lane_window_finish(const RxParams& p, uint32_t b
     lane_window_store<ST>(p, base, lane, s_rec_w);
 }
 
+// The kernel arguments a plain window reads, asked for in SGPRs at one point: the loads are then
+// issued together and waited for once (one s_waitcnt lgkmcnt ahead of the metadata loads), not sunk
+// to their uses in three dependent trips. The fused passes' arguments stay where the compiler puts them.
+template <int LAYOUT>
+__device__ __forceinline__ void lane_args(const RxParams& p) {
+    asm volatile("" ::"s"(p.bytes), "s"(p.n), "s"(p.flags), "s"(p.mac_lo), "s"(p.mac_hi), "s"(p.own_ip), "s"(p.out));
+    if constexpr (LAYOUT == 0 || LAYOUT == 3) asm volatile("" ::"s"(p.offsets_dw));
+    if constexpr (LAYOUT != 2) asm volatile("" ::"s"(p.lens));
+    if constexpr (LAYOUT == 1 || LAYOUT == 2) asm volatile("" ::"s"(p.stride));
+    if constexpr (LAYOUT == 2) asm volatile("" ::"s"(p.len));
+}
+
 template <int LAYOUT, int FUSE, int ST = kStorePlain>
 __device__ __forceinline__ void lane_window(const RxParams& p, uint32_t base, uint32_t lane, uint4* s_rec_w,
                                            Hist& hist, bool try_fast = true) {
@@ -203,6 +216,15 @@ __device__ __forceinline__ void lane_window(const RxParams& p, uint32_t base, ui
         // attempt's two exits into the general path's entry: as one if / else the blocks are laid out
         // general first, the attempt's loads stay live across all of it, and the kernel needs 87
         // VGPRs instead of 72.
+        // Tried and removed (part A): the outcome as a wave-uniform integer in an SGPR
+        // instead of a bool through readfirstlane. The join then writes no VGPR, needs no
+        // s_waitcnt vmcnt(0), and a plain window's wave ends with its record stores in flight (the
+        // failing exits wait where the general path first rewrites a loaded register). Alone, in the
+        // looping lean kernel: 1M x 64 B 18.56-18.88 -> 18.27-18.66 us, ranges overlap, median -0.20
+        // against a parent spread of 0.32; on top of the one-window kernel 18.11-18.55 -> 17.98-18.33,
+        // median -0.18: not told from noise either way (five interleaved rounds,
+        // profiles/r11/ab_one_window.log). Ending the wave at the stores with s_endpgm moved the
+        // fast blocks behind the general path: 58 -> 76 VGPRs.
         uint32_t done = __builtin_amdgcn_readfirstlane(lane_window_fast<FUSE, ST>(p, base, lane, st, s_rec_w, hist));
         asm volatile("" : "+s"(done));
         if (done == 1) return;
@@ -274,6 +296,30 @@ __global__ void __launch_bounds__(kLaneBlock) rx_lane_lean_kernel(const RxParams
     for (uint32_t base = wave * 64; base < p.n; base += nwaves * 64) {
         lane_window<LAYOUT, FUSE, kStoreLane>(p, base, lane, s_rec[w], hist, nwaves <= kLaneFastMaxWaves);
     }
+}
+
+// The lean instance for a launch whose grid covers the batch (launch_lane: every batch up to 2^30
+// frames): block b is one wave and takes window b, nothing else. Without the loop
+// the compiler no longer hoists the general path's constants (thirty scalar moves, eight v_dot2 of
+// constants) in front of the window: a plain window executes 8 scalar and 7 vector instructions
+// ahead of its metadata loads instead of 62 and 30, 126 VALU / 65 SALU per wave by the counters
+// instead of 154 / 91, in 58 VGPRs instead of 68. The fast path's size gate reads p.n, which here is
+// the grid: ceil(n / 64) <= kLaneFastMaxWaves. Launched with any other grid a block past the batch
+// would store outside it, so launch_lane alone chooses it. Five interleaved rounds against the
+// parent (profiles/r11/ab_one_window.log): 1M x 64 B 18.56-18.88 -> 18.11-18.55 us,
+// 4M 72.05-72.91 -> 71.99-72.92, 16M 279.6-280.3 -> 279.1-280.1. kLaneLdsPad 4096 / 5120 and
+// kLaneFastMaxWaves 262144 re-swept in the same job (on the build with lane_window's part A still in): no
+// default changes (4096 and 262144 lose 1-3 % at 16M, 5120 equals 4608).
+template <int LAYOUT, int FUSE>
+__global__ void __launch_bounds__(kLaneBlock) rx_lane_lean1_kernel(const RxParams p_in) {
+    static_assert(kLaneBlock == 64, "one wave per block");
+    __shared__ uint4 s_rec[128];
+    RxParams p = p_in;
+    p.hist = nullptr;
+    Hist hist{nullptr, 0, 0};
+    lane_args<LAYOUT>(p);
+    lane_window<LAYOUT, FUSE, kStoreLane>(p, blockIdx.x * 64u, threadIdx.x, s_rec, hist,
+                                          p.n <= kLaneFastMaxWaves * 64u);
 }
 
 // Several batches in one launch (halo_rx_parse_batches_device): the batch stream of the reference's
@@ -459,7 +505,10 @@ int launch_lane(const RxParams& p, int layout, int fuse, hipStream_t s) {
         // each: half the arrivals in the histogram tree, whose tail is a fixed cost per launch
         // (1M x 64 B: +2.1 instead of +2.7 us, 8192 blocks; 4096 gave no gain, profiles/r05/r5zm)
         if (p.hist && grid <= kHistHalveMax) grid = (grid + 1) / 2;
-        if (!p.hist)
+        // one window per wave whenever the grid covers the batch (always, below the grid cap)
+        if (!p.hist && (uint64_t)grid * 64u >= p.n)
+            hipLaunchKernelGGL((rx_lane_lean1_kernel<LAYOUT, FUSE>), dim3(grid), dim3(kLaneBlock), lane_dyn_lds(false), s, p);
+        else if (!p.hist)
             hipLaunchKernelGGL((rx_lane_lean_kernel<LAYOUT, FUSE>), dim3(grid), dim3(kLaneBlock), lane_dyn_lds(false), s, p);
         else
             hipLaunchKernelGGL((rx_lane_kernel<LAYOUT, FUSE>), dim3(grid), dim3(kLaneBlock), lane_dyn_lds(true), s, p);
