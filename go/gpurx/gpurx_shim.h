@@ -36,6 +36,18 @@ _Static_assert(sizeof(halo_kcp_summary_t) == 96, "halo_kcp_summary_t is 96 bytes
 _Static_assert(offsetof(halo_kcp_summary_t, ret_counts) == 16, "halo_kcp_summary_t.ret_counts");
 _Static_assert(offsetof(halo_kcp_summary_t, bytes_hashed) == 56, "halo_kcp_summary_t.bytes_hashed");
 _Static_assert(sizeof(halo_kcp_config_t) == 16, "halo_kcp_config_t is 16 bytes");
+// dhcp.go's DhcpMsg, DhcpSummary, DhcpLease, DhcpReply and DhcpClientEvent
+_Static_assert(sizeof(halo_dhcp_msg_t) == 128, "halo_dhcp_msg_t is 128 bytes");
+_Static_assert(offsetof(halo_dhcp_msg_t, yiaddr) == 16, "halo_dhcp_msg_t.yiaddr");
+_Static_assert(offsetof(halo_dhcp_msg_t, req_ip) == 32, "halo_dhcp_msg_t.req_ip");
+_Static_assert(offsetof(halo_dhcp_msg_t, mask_n) == 48, "halo_dhcp_msg_t.mask_n");
+_Static_assert(offsetof(halo_dhcp_msg_t, hostname) == 64, "halo_dhcp_msg_t.hostname");
+_Static_assert(sizeof(halo_dhcp_summary_t) == 64, "halo_dhcp_summary_t is 64 bytes");
+_Static_assert(sizeof(halo_dhcp_lease_t) == 80, "halo_dhcp_lease_t is 80 bytes");
+_Static_assert(sizeof(halo_dhcp_reply_t) == 32, "halo_dhcp_reply_t is 32 bytes");
+_Static_assert(offsetof(halo_dhcp_reply_t, req_ip) == 20, "halo_dhcp_reply_t.req_ip");
+_Static_assert(sizeof(halo_dhcp_client_event_t) == 24, "halo_dhcp_client_event_t is 24 bytes");
+_Static_assert(sizeof(halo_dhcp_config_t) == 24, "halo_dhcp_config_t is 24 bytes");
 
 // gpurx_netif: a halo_rx_netif_t from NetIf.MacAddr, IpAddrToU(NetIf.IpAddr), NatEnable.
 static inline halo_rx_netif_t gpurx_netif(const uint8_t* mac, uint32_t ip, int nat_enable) {
@@ -67,6 +79,21 @@ static inline halo_kcp_emit_config_t gpurx_kcp_emit_config(int byte_check_mode, 
     c.dgram_cap = dgram_cap;
     c.stream_cap = stream_cap;
     c.reserved = 0;
+    return c;
+}
+
+// gpurx_dhcp_config: a halo_dhcp_config_t from the NetIf's addresses (IpAddrToU form), MAC and switches.
+static inline halo_dhcp_config_t gpurx_dhcp_config(uint32_t ip, uint32_t network_mask, uint32_t dns, const uint8_t* mac,
+                                                   int server_enable, int client_enable, uint32_t capacity) {
+    halo_dhcp_config_t c;
+    memset(&c, 0, sizeof c);
+    c.ip = ip;
+    c.network_mask = network_mask;
+    c.dns = dns;
+    memcpy(c.mac, mac, 6);
+    c.server_enable = server_enable != 0;
+    c.client_enable = client_enable != 0;
+    c.capacity = capacity;
     return c;
 }
 

@@ -10,6 +10,7 @@ from ._lib import EGRESS_PORT_DTYPE  # noqa: F401
 from .arp import ArpTable  # noqa: F401
 from .deliver import DeliverResult, deliver, deliver_host, port_map  # noqa: F401
 from .kcp import KcpEmitResult, KcpIngestResult  # noqa: F401
+from .dhcp import DhcpBuildResult, DhcpDecodeResult, DhcpServer  # noqa: F401
 from .egress import EgressResult, egress_arp, egress_host, egress_masks, egress_switch  # noqa: F401
 from .nat import NatTable  # noqa: F401
 from .respond import RespondResult, build_replies, respond, respond_host, tcp_port_map  # noqa: F401  (adds ArpTable.encap_tx)
@@ -20,4 +21,5 @@ __all__ = ["PortMappingFlowTable", "forward_return_flows","ACTION", "ACTION_NAME
            "Switch", "EGRESS_PORT_DTYPE", "EgressResult", "egress_arp", "egress_host", "egress_masks", "egress_switch",
            "RespondResult", "build_replies", "respond", "respond_host", "tcp_port_map",
            "DeliverResult", "deliver", "deliver_host", "port_map",
-           "KcpIngestResult", "KcpEmitResult", "kcp"]
+           "KcpIngestResult", "KcpEmitResult", "kcp",
+           "DhcpServer", "DhcpDecodeResult", "DhcpBuildResult", "dhcp"]

@@ -207,6 +207,36 @@ assert (KCP_OUT_SESSION_DTYPE.itemsize, KCP_OUT_DGRAM_DTYPE.itemsize, KCP_EMIT_S
 KCP_EMIT_STATUS_NAMES = ("OK", "SEG_TOO_LONG", "BAD_MTU", "BAD_RANGE")
 KCP_EMIT_STATUS = {name: code for code, name in enumerate(KCP_EMIT_STATUS_NAMES)}
 KCP_EMIT_MAX = 1 << 23
+# DHCP: halo_dhcp_msg_t (128 bytes), halo_dhcp_summary_t (64), halo_dhcp_lease_t (80), halo_dhcp_reply_t (32),
+# halo_dhcp_client_event_t (24), HALO_DHCP_*
+DHCP_MSG_DTYPE = np.dtype([("index", "<u4"), ("status", "u1"), ("dir", "u1"), ("msg_type", "u1"), ("reserved0", "u1"),
+                           ("options", "<u4"), ("xid", "u1", (4,)), ("yiaddr", "<u4"), ("chaddr", "u1", (6,)),
+                           ("payload_len", "<u2"), ("remote_ip", "<u4"), ("req_ip", "<u4"), ("mask", "u1", (4,)),
+                           ("gateway", "u1", (4,)), ("dns", "u1", (4,)), ("mask_n", "u1"), ("gateway_n", "u1"),
+                           ("reserved1", "u1", (2,)), ("reserved2", "<u4", (3,)), ("hostname", "u1", (64,))])
+DHCP_SUMMARY_DTYPE = np.dtype([("msgs", "<u4"), ("msgs_written", "<u4"), ("status_counts", "<u4", (5,)),
+                               ("type_counts", "<u4", (9,))])
+DHCP_LEASE_DTYPE = np.dtype([("ip", "<u4"), ("mac", "u1", (6,)), ("reserved", "<u2"), ("exp_time", "<u4"),
+                             ("hostname", "u1", (64,))])
+DHCP_REPLY_DTYPE = np.dtype([("kind", "u1"), ("reserved0", "u1", (3,)), ("xid", "u1", (4,)), ("yiaddr", "<u4"),
+                             ("chaddr", "u1", (6,)), ("reserved1", "<u2"), ("req_ip", "<u4"), ("server_id", "<u4"),
+                             ("reserved2", "<u4")])
+DHCP_EVENT_DTYPE = np.dtype([("msg", "<u4"), ("ip", "<u4"), ("mask", "u1", (4,)), ("gateway", "u1", (4,)), ("dns", "u1", (4,)),
+                             ("mask_n", "u1"), ("gateway_n", "u1"), ("options", "u1"), ("reserved", "u1")])
+assert (DHCP_MSG_DTYPE.itemsize, DHCP_SUMMARY_DTYPE.itemsize, DHCP_LEASE_DTYPE.itemsize, DHCP_REPLY_DTYPE.itemsize,
+        DHCP_EVENT_DTYPE.itemsize) == (128, 64, 80, 32, 24)
+DHCP_STATUS_NAMES = ("OK", "PORTS", "SHORT", "COOKIE", "REF_PANIC")
+DHCP_STATUS = {name: code for code, name in enumerate(DHCP_STATUS_NAMES)}
+DHCP_TO_SERVER, DHCP_TO_CLIENT, DHCP_DIR_NONE = 0, 1, 2
+DHCP_OPT_MASK, DHCP_OPT_ROUTER, DHCP_OPT_DNS, DHCP_OPT_HOSTNAME = 0x01, 0x02, 0x04, 0x08
+DHCP_OPT_REQ_IP, DHCP_OPT_MSG_TYPE, DHCP_OPT_DNS_SHORT = 0x10, 0x20, 0x40
+DHCP_DISCOVER, DHCP_OFFER, DHCP_REQUEST, DHCP_ACK, DHCP_NAK, DHCP_RELEASE = 1, 2, 3, 5, 6, 7
+DHCP_H_NAMES = ("NONE", "OFFER", "NO_ADDR", "NO_REQ_IP", "NAK_ZERO", "NAK_SUBNET", "NAK_OTHER_MAC", "NAK_FULL", "ACK_NAK",
+                "REF_PANIC", "RELEASED", "RELEASE_ABSENT", "CLIENT_REQUEST", "CLIENT_ACK")
+DHCP_H = {name: code for code, name in enumerate(DHCP_H_NAMES)}
+DHCP_H_MASK, DHCP_H_F_REUSED, DHCP_H_F_REPLY = 0x0F, 0x40, 0x80
+DHCP_SLOT_BYTES = 288
+DHCP_BUILD_MAX = 1 << 23
 # halo_rx_ring_scan_t (24 bytes) and HALO_RING_STOP_* / HALO_RING_REGISTER
 RING_SCAN_DTYPE = np.dtype([("n_frames", "<u4"), ("stop", "<u4"), ("end_bytes", "<u8"), ("max_len", "<u4"),
                             ("pad", "<u4")])
@@ -380,6 +410,17 @@ class KcpEmitConfig(ctypes.Structure):
 
 
 assert ctypes.sizeof(KcpEmitConfig) == 24
+
+
+class DhcpConfig(ctypes.Structure):
+    """halo_dhcp_config_t."""
+
+    _fields_ = [("ip", ctypes.c_uint32), ("network_mask", ctypes.c_uint32), ("dns", ctypes.c_uint32),
+                ("mac", ctypes.c_uint8 * 6), ("server_enable", ctypes.c_uint8), ("client_enable", ctypes.c_uint8),
+                ("capacity", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(DhcpConfig) == 24
 
 
 class BatchDesc(ctypes.Structure):
@@ -602,6 +643,24 @@ _PROTOS = {
         _u8p, ctypes.c_uint64, ctypes.c_void_p]),
     "halo_kcp_emit_host": (ctypes.c_int, [
         ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint64, _u8p, _u8p, _u8p, _u8p, _u8p]),
+    "halo_dhcp_decode_workspace": (ctypes.c_uint64, [ctypes.c_uint32]),
+    "halo_dhcp_decode_device": (ctypes.c_int, [
+        _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, _u8p, ctypes.c_uint64, ctypes.c_void_p]),
+    "halo_dhcp_decode_host": (ctypes.c_int, [_u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p]),
+    "halo_dhcp_server_create": (ctypes.c_int, [ctypes.POINTER(DhcpConfig), ctypes.POINTER(ctypes.c_void_p)]),
+    "halo_dhcp_server_destroy": (None, [ctypes.c_void_p]),
+    "halo_dhcp_handle_msgs": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint64, _u8p, ctypes.c_uint32, _u8p, ctypes.POINTER(ctypes.c_uint32),
+        _u8p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_dhcp_list": (ctypes.c_uint32, [ctypes.c_void_p, _u8p, ctypes.c_uint32]),
+    "halo_dhcp_clear": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_uint64]),
+    "halo_dhcp_set_dns": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    "halo_dhcp_set_client_xid": (ctypes.c_int, [ctypes.c_void_p, _u8p]),
+    "halo_dhcp_discover": (ctypes.c_int, [ctypes.c_void_p, _u8p, _u8p]),
+    "halo_dhcp_server_config": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DhcpConfig)]),
+    "halo_dhcp_reply_build_device": (ctypes.c_int, [
+        ctypes.POINTER(DhcpConfig), _u8p, ctypes.c_uint32, _u8p, _u8p, ctypes.c_void_p]),
+    "halo_dhcp_reply_build_host": (ctypes.c_int, [ctypes.POINTER(DhcpConfig), _u8p, ctypes.c_uint32, _u8p, _u8p]),
     "halo_synth_layout": (ctypes.c_int, [
         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint64)]),

@@ -972,7 +972,7 @@ HALO_API int halo_switch_debug_set_epoch(halo_switch_t* sw, uint32_t epoch);
  * below) writes the padded copy and the per-port index lists.
  * Locally originated packets take TxIpv4's variant of the step, halo_arp_encap_tx_device, on the
  * frames halo_tx_build_batch_device built ("local responders" below).
- * Not covered: Router.Ipv4PktFwdHook; compact records in the gather; DHCP;
+ * Not covered: Router.Ipv4PktFwdHook; compact records in the gather (DHCP: its own section below);
  * UDP service replies (the handlers' job); sending the LoChan copy of a LOOPBACK. */
 typedef struct halo_arp_table halo_arp_table_t;
 #define HALO_ARP_MAX_NETIFS 64u
@@ -1172,7 +1172,7 @@ HALO_API int halo_arp_gather_device(const uint8_t* d_bytes, const uint32_t* d_of
  * where halo_pmflow_record overwrites it identically: results do not depend on the sync cadence.
  * FAILURE: argument errors (HALO_E_INVAL / _RANGE) leave the table as it was and are checked before
  * a device is looked for. A library built without the device side answers HALO_E_NODEV to the
- * *_device calls. Not covered: Router.Ipv4PktFwdHook; DHCP; device-side inserts (order and the
+ * *_device calls. Not covered: Router.Ipv4PktFwdHook; device-side inserts (order and the
  * capacity check depend on frame order, as NatAddFlow's do); interface names. */
 typedef struct halo_pmflow_table halo_pmflow_table_t;
 typedef struct halo_pmflow_config {
@@ -1573,7 +1573,7 @@ HALO_API int halo_rx_dispatch_loopback(const halo_rx_result_t* results, uint32_t
  * halo_arp_encap_tx_device -> halo_tx_egress_arp_device. A reply that then gets NO_ROUTE, MISS or
  * OWN_IP has still consumed its iphId (BuildIpv4Pkt runs before FindRoute): build every descriptor,
  * drop afterwards.
- * Not covered: Router.Ipv4PktFwdHook; DHCP; UDP service replies (the
+ * Not covered: Router.Ipv4PktFwdHook; UDP service replies (the
  * handlers' job); sending the LoChan copy of a LOOPBACK reply.
  * The device call: three launches on `stream` (tile counts, scan, scatter), every argument checked
  * before a device is looked for. Alignment: d_records 16; d_desc, d_src 8; offsets, ops, ports map,
@@ -1624,8 +1624,8 @@ HALO_API int halo_tx_respond_host(const uint32_t* offsets_dw, const uint16_t* le
  *         empty payloads included (the handshake answers themselves are the responders')
  *                                                                   engine/tcp_engine.go:10-26
  *   DHCP  a == BCAST_UDP, dport == 67 or 68 (DhcpServerPort / DhcpClientPort) and HALO_DELIVER_DHCP
- *         in cfg->flags: RxDhcp(udpPayload, udpSrcPort, udpDstPort, ipv4SrcAddr). The DHCP engine
- *         stays on the host.                                        engine/udp_engine.go:35-44
+ *         in cfg->flags: RxDhcp(udpPayload, udpSrcPort, udpDstPort, ipv4SrcAddr). "DHCP" below
+ *         decodes these records where they lie.                     engine/udp_engine.go:35-44
  * d_udp_ports / d_tcp_ports are 65,536 bits as 2,048 u32, bit p & 31 of word p >> 5, as
  * halo_tx_respond_device takes them; NULL = no service of that protocol. With HALO_RX_L3_START in
  * cfg->flags the records are LoChan packets (engine/engine.go:353-381): the action is
@@ -1658,7 +1658,7 @@ HALO_API int halo_tx_respond_host(const uint32_t* offsets_dw, const uint16_t* le
  * summary, index, workspace: 8; bytes, maps, offsets: 4; lens: 2), workspace_bytes <
  * halo_rx_deliver_workspace(n). HALO_E_NODEV / _ARCH as elsewhere.
  * Not covered: a stream per service (the order the reference shows is the batch's; local_port and
- * kind let a host split it); the DHCP engine. */
+ * kind let a host split it). The DHCP engine: "DHCP" below. */
 #define HALO_DELIVER_UDP 0u
 #define HALO_DELIVER_TCP 1u
 #define HALO_DELIVER_DHCP 2u /* the kind, and the bit of halo_deliver_config_t.flags that enables it */
@@ -1965,6 +1965,240 @@ HALO_API int halo_kcp_emit_host(const halo_kcp_emit_config_t* cfg, const halo_kc
                                 uint32_t n_sessions, const halo_kcp_seg_t* segs, uint32_t n_segs, const uint8_t* payload,
                                 uint64_t payload_bytes, uint8_t* stream, halo_kcp_out_dgram_t* dgrams,
                                 halo_tx_build_desc_t* descs, uint8_t* status, halo_kcp_emit_summary_t* summary);
+
+/* ---- DHCP: batched message decode, the lease table and the reply build -------------------------
+ * engine/dhcp_engine.go, the reference's other in-tree service: RxDhcp (called from the receive
+ * loop through RxUdpBroadcast), TxDhcp -> TxUdp -> TxIpv4's broadcast branch, ListDhcp and
+ * DhcpLeaseClear. Three pieces: the stateless per-byte work runs where the bytes lie (DECODE over a
+ * delivery stream, REPLY BUILD into the payloads and descriptors halo_tx_build_batch_device
+ * takes), and a host control plane (the SERVER object: lease table and state machine) is the
+ * authority; it works from 128-byte message descriptors and never touches a payload.
+ *
+ * DECODE. INPUT: halo_rx_deliver_*'s stream, summary and index, as "KCP ingest" takes them.
+ *   Considered: index entries k < min(summary.records, index_cap) with offset != 0xFFFFFFFF (the
+ *   record count is read where the stream lies). SELECTED: those whose header says kind ==
+ *   HALO_DELIVER_DHCP. One halo_dhcp_msg_t per selected record, in stream order (RxDhcp's first
+ *   lines, ParseDhcpPkt and ParseDhcpOption: dhcp_engine.go:216-230, :169-181, :70-122):
+ *   direction  remote_port == 68 && local_port == 67: TO_SERVER; 67 -> 68: TO_CLIENT; any other
+ *              pair: status PORTS (the reference does not parse it: only the header is read).
+ *   payload_len < 240: SHORT. Bytes 236..239 not 63 82 53 63: COOKIE. Both leave every payload
+ *              field of the record zero (ParseDhcpPkt returns nothing).
+ *   xid = pkt[4:8] as raw bytes, yiaddr = IpAddrToU(pkt[16:20]), chaddr = pkt[28:34].
+ *   options    ParseDhcpOption's loop over o = payload[240:], n = len(o), i = 0: stop when o[i] ==
+ *              0xff; stop when i + 1 >= n (one byte remains); code = o[i], length = o[i + 1]; stop
+ *              when i + 2 + length > n; keep codes 1, 3, 6, 12, 50, 53 (of a repeated code the last
+ *              wins: the map entry is overwritten); i += 2 + length. Code 0 is an ordinary TLV.
+ *   REF_PANIC  where the Go code would panic (HALO_ROUTE_PANIC is the precedent): the loop top
+ *              reaches i == n (an empty option area, or an option that ends exactly at the end
+ *              with no 0xff before it), or a code 53 has length 0 (data[0]), wherever it stands.
+ *              Every option field of such a record is zero.
+ *   fields     msg_type = option 53's data[0]; req_ip = IpAddrToU(option 50's data): 0 when its
+ *              length is not 4; mask / gateway = the first min(length, 4) bytes of options 1 / 3
+ *              and that count (what copy(i.NetworkMask, ..) / copy(i.Gateway, ..) take); dns =
+ *              option 6's first four bytes; hostname = option 12 in mem.StaticString64 form:
+ *              min(length, 63) bytes, zeros, the count in byte 63.
+ *              BUILD-DEFINED: option 6 with length < 4 — `data[0:4]` reslices into the capacity
+ *              of the caller's buffer, which this stage cannot know — counts as ABSENT, with
+ *              HALO_DHCP_OPT_DNS_SHORT set; both bits describe the LAST option 6.
+ *   A missing option 53 is no status: HALO_DHCP_OPT_MSG_TYPE is clear and the handler returns
+ *   silently, as RxDhcp does.
+ * CAPACITY (the egress rule): messages are written while they fit msg_cap; `msgs` stays the total.
+ *   status_counts / type_counts describe the WRITTEN messages (type_counts[t]: OK messages with
+ *   option 53 and msg_type t <= 8; type_counts[0] also counts every other OK message).
+ * READS: nothing outside the 4-byte words that hold a selected record's header and payload bytes,
+ *   the delivery summary and the considered index entries; of a PORTS record only the header. The
+ *   stream is never written. WRITES: the written prefix and the summary (SET; nothing is cleared
+ *   beforehand), nothing else.
+ * The device call is asynchronous on `stream` with no host round trip: three launches (per-tile
+ * counts from the headers' kind alone, the scan over tiles that writes the summary, the write with
+ * the walk). Arguments are checked before any device call. HALO_E_INVAL: a null summary /
+ * deliver_summary; with index_cap > 0 a null stream or index; a null msgs with msg_cap > 0; for
+ * the device call a misaligned array (msgs: 16; index, both summaries, workspace: 8; stream: 4), a
+ * null workspace with index_cap > 0 or workspace_bytes < halo_dhcp_decode_workspace(index_cap).
+ * index_cap == 0, or an empty delivery, zeroes the summary. A build without HIP answers
+ * HALO_E_NODEV. */
+#define HALO_DHCP_OK 0u
+#define HALO_DHCP_PORTS 1u     /* neither 68 -> 67 nor 67 -> 68                         */
+#define HALO_DHCP_SHORT 2u     /* "dhcp packet len < 240 bytes"                         */
+#define HALO_DHCP_COOKIE 3u    /* "dhcp magic cookie error"                             */
+#define HALO_DHCP_REF_PANIC 4u /* the reference would panic in ParseDhcpOption          */
+#define HALO_DHCP_STATUS_COUNT 5u
+#define HALO_DHCP_TO_SERVER 0u
+#define HALO_DHCP_TO_CLIENT 1u
+#define HALO_DHCP_DIR_NONE 2u  /* with status PORTS */
+#define HALO_DHCP_OPT_MASK 0x01u      /* option 1 present  */
+#define HALO_DHCP_OPT_ROUTER 0x02u    /* option 3          */
+#define HALO_DHCP_OPT_DNS 0x04u       /* option 6, length >= 4 */
+#define HALO_DHCP_OPT_HOSTNAME 0x08u  /* option 12         */
+#define HALO_DHCP_OPT_REQ_IP 0x10u    /* option 50         */
+#define HALO_DHCP_OPT_MSG_TYPE 0x20u  /* option 53         */
+#define HALO_DHCP_OPT_DNS_SHORT 0x40u /* the last option 6 had length < 4: build-defined absent */
+#define HALO_DHCP_DISCOVER 1u /* DhcpOptionMsgType*: msg_type, and halo_dhcp_reply_t.kind */
+#define HALO_DHCP_OFFER 2u
+#define HALO_DHCP_REQUEST 3u
+#define HALO_DHCP_ACK 5u
+#define HALO_DHCP_NAK 6u
+#define HALO_DHCP_RELEASE 7u
+#define HALO_DHCP_TYPE_COUNT 9u
+typedef struct halo_dhcp_msg {
+    uint32_t index;       /* k: the message's entry in the delivery index                    */
+    uint8_t status;       /* HALO_DHCP_OK .. _REF_PANIC                                      */
+    uint8_t dir;          /* HALO_DHCP_TO_SERVER / _TO_CLIENT / _DIR_NONE                    */
+    uint8_t msg_type;     /* option 53's data[0]                                             */
+    uint8_t reserved0;    /* 0                                                               */
+    uint32_t options;     /* HALO_DHCP_OPT_*                                                 */
+    uint8_t xid[4];       /* pkt[4:8]                                                        */
+    uint32_t yiaddr;      /* IpAddrToU(pkt[16:20])                                           */
+    uint8_t chaddr[6];    /* pkt[28:34]                                                      */
+    uint16_t payload_len; /* the delivery header's                                           */
+    uint32_t remote_ip;   /* the delivery header's: RxDhcp's ipv4SrcAddr                     */
+    uint32_t req_ip;      /* IpAddrToU(option 50's data)                                     */
+    uint8_t mask[4];      /* option 1: the first mask_n bytes, zeros behind them             */
+    uint8_t gateway[4];   /* option 3: the first gateway_n bytes                             */
+    uint8_t dns[4];       /* option 6's data[0:4]                                            */
+    uint8_t mask_n;       /* min(option 1's length, 4)                                       */
+    uint8_t gateway_n;    /* min(option 3's length, 4)                                       */
+    uint8_t reserved1[2]; /* 0 */
+    uint32_t reserved2[3]; /* 0 */
+    uint8_t hostname[64]; /* option 12 as mem.StaticString64                                 */
+} halo_dhcp_msg_t;        /* 128 B */
+typedef struct halo_dhcp_summary { /* SET by the call */
+    uint32_t msgs;         /* selected records, also beyond msg_cap */
+    uint32_t msgs_written;
+    uint32_t status_counts[HALO_DHCP_STATUS_COUNT]; /* of the written messages */
+    uint32_t type_counts[HALO_DHCP_TYPE_COUNT];
+} halo_dhcp_summary_t;     /* 64 B */
+/* Bytes of device workspace (8-byte aligned, no initialisation). One workspace serves any number
+ * of calls issued on one stream. */
+HALO_API uint64_t halo_dhcp_decode_workspace(uint32_t index_cap);
+HALO_API int halo_dhcp_decode_device(const uint8_t* d_stream, const halo_deliver_summary_t* d_deliver_summary,
+                                     const halo_deliver_index_t* d_index, uint32_t index_cap, halo_dhcp_msg_t* d_msgs,
+                                     uint32_t msg_cap, halo_dhcp_summary_t* d_summary, void* d_workspace,
+                                     uint64_t workspace_bytes, halo_stream_t stream);
+/* The same outputs from the sequential loop over host memory; no HIP. Picked by name, never a
+ * fallback. Arrays need no alignment. */
+HALO_API int halo_dhcp_decode_host(const uint8_t* stream, const halo_deliver_summary_t* deliver_summary,
+                                   const halo_deliver_index_t* index, uint32_t index_cap, halo_dhcp_msg_t* msgs,
+                                   uint32_t msg_cap, halo_dhcp_summary_t* summary);
+
+/* THE SERVER OBJECT: one per NetIf, as DhcpLeaseTable is; host memory, no HIP, not thread safe (the
+ * reference's DhcpLock is the caller's). It restates dhcp_engine.go:216-434 call for call:
+ *   a message whose status is not OK, whose direction's side is disabled or that has no option 53
+ *   does nothing. TO_SERVER (server_enable):
+ *   DISCOVER  reuses req_ip only when a lease for it exists with the same MAC; otherwise the first
+ *             networkU + ii (u32 arithmetic), ii < 2^hostBits, hostBits = 32 - popcount(networkU) —
+ *             the popcount of the network ADDRESS, as written; nothing is scanned when hostBits ==
+ *             32 — whose last octet is neither 0 nor 255, that is not the own address and not
+ *             leased. It records no lease. No address: no reply. Else one OFFER.
+ *   REQUEST   no option 50: nothing. req_ip == 0, another subnet, leased to another MAC, or a new
+ *             lease with the table at `capacity` (MallocType returning nil): NAK, in this order.
+ *             Otherwise the lease is written (ExpTime = (uint32_t)(now + 3600), the hostname by
+ *             StaticString64.Set: a renewed lease keeps the bytes behind a shorter name) and the
+ *             replies are ACK FOLLOWED BY NAK: the dhcp_nak label sits directly behind the ACK's
+ *             TxDhcp, so the reference falls through. A REQUEST that reaches HostName.Set with an
+ *             empty hostname (option 12 absent or of length 0) is REF_PANIC: Set("") indexes
+ *             element 0 of an empty slice (mem/static_allocator.go:219); no state change, no reply.
+ *   RELEASE   deletes the lease keyed by remote_ip, whatever the MAC.
+ *   TO_CLIENT (client_enable, own ip 0, xid equal to the client's transaction id):
+ *   OFFER     one REQUEST reply (option 50 = yiaddr, option 54 = remote_ip).
+ *   ACK       one halo_dhcp_client_event_t. The caller applies it (the NetIf's address, the two
+ *             AddRoute calls, the DNS copy to the serving NetIfs, SendFreeArp) and, as the
+ *             reference's own address is set from then on, ignores what follows it.
+ * halo_dhcp_handle_msgs handles msgs[0..n) in order. verdicts[i] (optional) = a HALO_DHCP_H_*
+ * code | flag bits. reply_cap must be at least 2 * n, and event_cap at least n unless events is
+ * NULL with event_cap 0 (events are then counted, not stored): else HALO_E_INVAL, before any
+ * state changes. halo_dhcp_list copies up to cap leases in ascending address order (ListDhcp; the
+ * reference's order is its table's) and returns the count. halo_dhcp_clear is one DhcpLeaseClear tick:
+ * leases with now > ExpTime, in plain u32, are deleted; returns how many. halo_dhcp_discover is
+ * DhcpDiscover with the caller's random xid: it sets the client's transaction id and gives the
+ * DISCOVER message. */
+#define HALO_DHCP_H_NONE 0u          /* nothing to do (status, side disabled, no / other msg type, xid) */
+#define HALO_DHCP_H_OFFER 1u
+#define HALO_DHCP_H_NO_ADDR 2u       /* "dhcp server no ip found"                                     */
+#define HALO_DHCP_H_NO_REQ_IP 3u     /* REQUEST without option 50                                     */
+#define HALO_DHCP_H_NAK_ZERO 4u
+#define HALO_DHCP_H_NAK_SUBNET 5u
+#define HALO_DHCP_H_NAK_OTHER_MAC 6u
+#define HALO_DHCP_H_NAK_FULL 7u
+#define HALO_DHCP_H_ACK_NAK 8u       /* the lease is written; ACK, then NAK                           */
+#define HALO_DHCP_H_REF_PANIC 9u     /* HostName.Set("")                                              */
+#define HALO_DHCP_H_RELEASED 10u
+#define HALO_DHCP_H_RELEASE_ABSENT 11u
+#define HALO_DHCP_H_CLIENT_REQUEST 12u
+#define HALO_DHCP_H_CLIENT_ACK 13u
+#define HALO_DHCP_H_MASK 0x0Fu
+#define HALO_DHCP_H_F_REUSED 0x40u   /* DISCOVER: the requested lease is offered again; REQUEST: a renewal */
+#define HALO_DHCP_H_F_REPLY 0x80u    /* at least one reply was written                                */
+typedef struct halo_dhcp_config {
+    uint32_t ip;           /* IpAddrToU(NetIf.IpAddr); 0 for a client that has none yet   */
+    uint32_t network_mask; /* IpAddrToU(NetIf.NetworkMask)                               */
+    uint32_t dns;          /* IpAddrToU(NetIf.DnsServerAddr)                             */
+    uint8_t mac[6];        /* NetIf.MacAddr                                              */
+    uint8_t server_enable; /* Config.DhcpServerEnable                                    */
+    uint8_t client_enable; /* Config.DhcpClientEnable                                    */
+    uint32_t capacity;     /* the most leases: the stand-in for MallocType returning nil */
+} halo_dhcp_config_t;      /* 24 B */
+typedef struct halo_dhcp_lease {
+    uint32_t ip;          /* IpAddrToU(DhcpLease.IpAddr) */
+    uint8_t mac[6];
+    uint16_t reserved;    /* 0 */
+    uint32_t exp_time;
+    uint8_t hostname[64]; /* mem.StaticString64 */
+} halo_dhcp_lease_t;      /* 80 B */
+typedef struct halo_dhcp_reply {
+    uint8_t kind;        /* HALO_DHCP_OFFER / _ACK / _NAK / _REQUEST / _DISCOVER */
+    uint8_t reserved0[3];
+    uint8_t xid[4];
+    uint32_t yiaddr;     /* IpAddrToU form; 0 for NAK / REQUEST / DISCOVER */
+    uint8_t chaddr[6];
+    uint16_t reserved1;
+    uint32_t req_ip;     /* REQUEST: option 50 */
+    uint32_t server_id;  /* REQUEST: option 54 */
+    uint32_t reserved2;
+} halo_dhcp_reply_t;     /* 32 B */
+typedef struct halo_dhcp_client_event {
+    uint32_t msg;       /* the ACK's position in msgs */
+    uint32_t ip;        /* yiaddr */
+    uint8_t mask[4], gateway[4], dns[4];
+    uint8_t mask_n, gateway_n;
+    uint8_t options;    /* HALO_DHCP_OPT_MASK | _ROUTER | _DNS: which were present */
+    uint8_t reserved;
+} halo_dhcp_client_event_t; /* 24 B */
+typedef struct halo_dhcp_server halo_dhcp_server_t;
+HALO_API int halo_dhcp_server_create(const halo_dhcp_config_t* cfg, halo_dhcp_server_t** out);
+HALO_API void halo_dhcp_server_destroy(halo_dhcp_server_t* s);
+HALO_API int halo_dhcp_handle_msgs(halo_dhcp_server_t* s, const halo_dhcp_msg_t* msgs, uint32_t n, uint64_t now,
+                                   halo_dhcp_reply_t* replies, uint32_t reply_cap, uint8_t* verdicts, uint32_t* n_replies,
+                                   halo_dhcp_client_event_t* events, uint32_t event_cap, uint32_t* n_events);
+HALO_API uint32_t halo_dhcp_list(const halo_dhcp_server_t* s, halo_dhcp_lease_t* out, uint32_t cap);
+HALO_API uint32_t halo_dhcp_clear(halo_dhcp_server_t* s, uint64_t now);
+HALO_API int halo_dhcp_set_dns(halo_dhcp_server_t* s, uint32_t dns);
+HALO_API int halo_dhcp_set_client_xid(halo_dhcp_server_t* s, const uint8_t xid[4]);
+HALO_API int halo_dhcp_discover(halo_dhcp_server_t* s, const uint8_t xid[4], halo_dhcp_reply_t* reply);
+HALO_API int halo_dhcp_server_config(const halo_dhcp_server_t* s, halo_dhcp_config_t* out);
+
+/* REPLY BUILD: from n reply descriptors and the server's addresses (cfg: ip, network_mask, dns) to
+ * the UDP payloads BuildDhcpPkt makes and one halo_tx_build_desc_t per reply, ready for
+ * halo_tx_build_batch_device. Reply i lies at i * HALO_DHCP_SLOT_BYTES of the payload buffer, the
+ * slot's tail zero. Lengths: 286 OFFER / ACK, 250 NAK, 270 REQUEST, 258 DISCOVER. The descriptor:
+ * payload_off = i * 288, payload_len, proto 17, ports 67 -> 68 (OFFER / ACK / NAK) or 68 -> 67,
+ * src_ip = cfg->ip, dst_ip 255.255.255.255, dst_mac ff:ff:ff:ff:ff:ff, HALO_TX_BUILD_ETH, the rest
+ * zero: TxIpv4's dst[3] == 255 branch, so no ARP step follows. A reply of any other kind gives a
+ * zero slot and an all-zero descriptor (proto 0: halo_tx_build answers HALO_TX_B_PROTO).
+ * OPTION ORDER: BuildDhcpOption ranges over a Go map, so the reference's order is random per
+ * packet. This build fixes it to the order of the map literals in the source — 53, 1, 3, 6, 51,
+ * 59, 58, 54 for OFFER / ACK (lease 3600, rebinding 3150, renewal 1800); 53, 54 for NAK; 53, 61, 50,
+ * 54, 55 for REQUEST; 53, 61, 55 for DISCOVER; then 0xff — an order the reference can produce, not
+ * the only one.
+ * One launch, asynchronous on `stream`; fixed slots, so no scan and one writer per dword. WRITES:
+ * [0, n * 288) of d_payload and descs[0..n). HALO_E_INVAL: a null cfg; with n > 0 a null array; n
+ * above 2^23; for the device call a misaligned array (d_replies: 16; d_descs: 8; d_payload: 4). */
+#define HALO_DHCP_SLOT_BYTES 288u
+#define HALO_DHCP_BUILD_MAX (1u << 23)
+HALO_API int halo_dhcp_reply_build_device(const halo_dhcp_config_t* cfg, const halo_dhcp_reply_t* d_replies, uint32_t n,
+                                          uint8_t* d_payload, halo_tx_build_desc_t* d_descs, halo_stream_t stream);
+HALO_API int halo_dhcp_reply_build_host(const halo_dhcp_config_t* cfg, const halo_dhcp_reply_t* replies, uint32_t n,
+                                        uint8_t* payload, halo_tx_build_desc_t* descs);
 
 /* ---- synthetic traffic (bench + tests; SURVEY.md §8d generator) ----------------------
  * Every field of frame i is a pure function of (seed, i), so any shard of the global
