@@ -97,6 +97,18 @@ static inline halo_dhcp_config_t gpurx_dhcp_config(uint32_t ip, uint32_t network
     return c;
 }
 
+// gpurx_lo_config: a halo_lo_config_t for the loopback gather (tx: HALO_LO_TX, jumbo: HALO_RX_JUMBO_EXT).
+static inline halo_lo_config_t gpurx_lo_config(uint32_t n_netifs, int tx, int jumbo, uint64_t region_bytes,
+                                               uint32_t index_cap) {
+    halo_lo_config_t c;
+    memset(&c, 0, sizeof c);
+    c.n_netifs = n_netifs;
+    c.flags = (tx ? HALO_LO_TX : 0u) | (jumbo ? HALO_RX_JUMBO_EXT : 0u);
+    c.region_bytes = region_bytes;
+    c.index_cap = index_cap;
+    return c;
+}
+
 // gpurx_parse_one: one frame (l3 = 0) or one bare IPv4 packet (l3 = 1) through the host entry
 // point, as a batch of one. The netif only sets the dispatch flags, which the Parse* wrappers
 // do not read.

@@ -16,10 +16,12 @@ from .nat import NatTable  # noqa: F401
 from .respond import RespondResult, build_replies, respond, respond_host, tcp_port_map  # noqa: F401  (adds ArpTable.encap_tx)
 from .switch import Switch  # noqa: F401
 from .pmflow import PortMappingFlowTable, forward_return_flows  # noqa: F401  (adds ArpTable.encap_via)
+from .loopback import LoResult  # noqa: F401
+from . import loopback  # noqa: F401
 
 __all__ = ["PortMappingFlowTable", "forward_return_flows","ACTION", "ACTION_NAMES", "RESULT_DTYPE", "STATUS", "STATUS_NAMES", "NetIf", "HaloError", "ArpTable", "NatTable",
            "Switch", "EGRESS_PORT_DTYPE", "EgressResult", "egress_arp", "egress_host", "egress_masks", "egress_switch",
            "RespondResult", "build_replies", "respond", "respond_host", "tcp_port_map",
            "DeliverResult", "deliver", "deliver_host", "port_map",
            "KcpIngestResult", "KcpEmitResult", "kcp",
-           "DhcpServer", "DhcpDecodeResult", "DhcpBuildResult", "dhcp"]
+           "DhcpServer", "DhcpDecodeResult", "DhcpBuildResult", "dhcp", "LoResult", "loopback"]

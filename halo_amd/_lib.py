@@ -159,6 +159,8 @@ PMFLOW_V_COUNT = len(PMFLOW_VERDICT_NAMES)
 EGRESS_PORT_DTYPE = np.dtype([("frames", "<u4"), ("frames_written", "<u4"), ("bytes", "<u8"), ("bytes_written", "<u8")])
 assert EGRESS_PORT_DTYPE.itemsize == 24
 EGRESS_MAX_PORTS = 64
+HALO_LO_TX = 0x100  # halo_lo_config_t.flags: tx mode
+LO_NOT_WRITTEN = 0xFFFFFFFF  # d_pkt_off_dw of a packet beyond the written prefix
 EGRESS_KIND_MASKS, EGRESS_KIND_ARP, EGRESS_KIND_SWITCH = 0, 1, 2
 # the local responders: halo_respond_src_t (8 bytes), HALO_RESPOND_*
 RESPOND_SRC_DTYPE = np.dtype([("index", "<u4"), ("kind", "u1"), ("pad", "u1", (3,))])
@@ -371,6 +373,13 @@ class PmflowConfig(ctypes.Structure):
 
     _fields_ = [("n_netifs", ctypes.c_uint32), ("netif", NetIf * 64), ("gateway", ctypes.c_uint32 * 64),
                 ("capacity", ctypes.c_uint32), ("capacity_log2", ctypes.c_uint32)]
+
+
+class LoConfig(ctypes.Structure):
+    """halo_lo_config_t."""
+
+    _fields_ = [("n_netifs", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("region_bytes", ctypes.c_uint64),
+                ("index_cap", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class EgressConfig(ctypes.Structure):
@@ -661,6 +670,14 @@ _PROTOS = {
     "halo_dhcp_reply_build_device": (ctypes.c_int, [
         ctypes.POINTER(DhcpConfig), _u8p, ctypes.c_uint32, _u8p, _u8p, ctypes.c_void_p]),
     "halo_dhcp_reply_build_host": (ctypes.c_int, [ctypes.POINTER(DhcpConfig), _u8p, ctypes.c_uint32, _u8p, _u8p]),
+    "halo_arp_loopback_mark_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, _u8p, ctypes.c_void_p]),
+    "halo_lo_gather_workspace": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    "halo_lo_gather_device": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_uint64,
+        ctypes.c_void_p]),
+    "halo_lo_gather_host": (ctypes.c_int, [
+        ctypes.c_void_p, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p, _u8p]),
     "halo_synth_layout": (ctypes.c_int, [
         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.POINTER(ctypes.c_uint64)]),

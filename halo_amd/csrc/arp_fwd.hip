@@ -3,7 +3,9 @@
 // step (engine/ipv4_engine.go:180-201, :226-236, :267: route id -> next hop -> GetArpCache -> the
 // Ethernet header BuildEthFrm writes) over a device-resident batch — also with the out-interface
 // override of a port-mapping return flow (:180-186, halo_arp_encap_via_device; pmflow_fwd.hip makes
-// the via array) — and the gather that brings a parsed batch's ARP messages to the host in frame order.
+// the via array) — that step's LOOPBACK test alone, from records, for the chain to take ahead of the
+// NAT lookup (halo_arp_loopback_mark_device; lo_gather.hip makes the LoChan batches), and the gather
+// that brings a parsed batch's ARP messages to the host in frame order.
 //
 // Layout: a power-of-two array of 16-byte slots {ip, used | netif, mac[0..3], mac[4..5]} placed by
 // linear probing from key_hash(netif, ip) & mask, the hash the host compile shares. A probe is one
@@ -275,6 +277,29 @@ __global__ void __launch_bounds__(kGatherTile) arp_scatter_kernel(const uint8_t*
     o[4] = make_uint2(q[4] >> 16 | q[5] << 16, q[5] >> 16 | h40 << 16);
 }
 
+// The encap's LOOPBACK test alone, from records, ahead of the NAT lookup (halo_arp_loopback_mark_device):
+// no frame byte is touched. One lane per record, one 16-byte load of its first half {status ..,
+// ip_proto .., src_ip, dst_ip}, one byte store. nat = the in NetIf's nat_enable.
+__global__ void __launch_bounds__(256) arp_loopback_mark_kernel(const ArpView v, const uint4* __restrict__ recs, uint32_t n,
+                                                                const uint32_t* __restrict__ route_ids, uint32_t nat,
+                                                                const uint2* __restrict__ via, uint8_t* __restrict__ mark) {
+    for (uint32_t base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u) {
+        const uint32_t i = base + threadIdx.x;
+        if (i >= n) continue;
+        const uint4 rec = recs[2ull * i];
+        const uint32_t rid = route_ids[i];
+        uint32_t out = 0xFFFFFFFFu;
+        if (rid < v.n_routes) out = v.routes[rid].netif;
+        if (via) {
+            const uint32_t w = via[i].x;  // verdict | wan_netif << 8 | wan_port << 16
+            if ((w & 0xFFu) == HALO_PMFLOW_V_OVERRIDE) out = (w >> 8) & 0xFFu;
+        }
+        bool m = false;
+        if (!nat && (rec.y & 0xFFu) != 0xFFu && out < v.n_netifs) m = rec.w == v.netifs[out].ip;
+        mark[i] = m ? 1 : 0;
+    }
+}
+
 uint32_t arp_blocks(uint64_t threads) {
     const uint64_t b = (threads + 255) / 256;
     const uint64_t kMax = 256ull * 8;  // 8 workgroups per CU; twice as many measured 9 us slower at 2^20 frames
@@ -400,6 +425,26 @@ int ops_encap(const halo_arp_table* t, uint8_t* d_bytes, const uint32_t* d_offse
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }
 
+int ops_mark(const halo_arp_table* t, const halo_rx_result_t* d_records, uint32_t n, const uint32_t* d_route_ids,
+             uint32_t in_netif, const halo_pmflow_via_t* d_via, uint8_t* d_mark, halo_stream_t stream) {
+    ArpDevice* d = dev_of<ArpDevice>(t);
+    if (!d) return HALO_E_INVAL;  // never synced
+    std::shared_lock<std::shared_mutex> lk(d->view_mu);
+    ArpView v;
+    if (arp_view(t, d, &v) || !v.routes) return HALO_E_INVAL;  // ... or synced without a route table
+    if (n == 0) return HALO_OK;
+    if (!d_records || !d_route_ids || !d_mark) return HALO_E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(d_records) & 15u) || (reinterpret_cast<uintptr_t>(d_route_ids) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_via) & 7u))
+        return HALO_E_INVAL;
+    const int rc = check_device();
+    if (rc) return rc;
+    hipLaunchKernelGGL(arp_loopback_mark_kernel, dim3(arp_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), v,
+                       reinterpret_cast<const uint4*>(d_records), n, d_route_ids, t->cfg.netif[in_netif].nat_enable ? 1u : 0u,
+                       reinterpret_cast<const uint2*>(d_via), d_mark);
+    return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
+}
+
 int ops_gather(const uint8_t* d_bytes, const uint32_t* d_offsets_dw, const uint16_t* /*d_lens*/,
                const halo_rx_result_t* d_records, uint32_t n, uint32_t netif, halo_arp_msg_t* d_msgs, uint32_t cap,
                uint32_t* d_count, void* d_workspace, uint64_t /*workspace_bytes*/, halo_stream_t stream) {
@@ -417,7 +462,8 @@ int ops_gather(const uint8_t* d_bytes, const uint32_t* d_offsets_dw, const uint1
 }
 
 const arp::DeviceOps kDeviceOps = {
-    ops_sync, publish_entry<ArpDevice, halo_arp_table>, destroy<ArpDevice, halo_arp_table>, ops_lookup, ops_encap, ops_gather};
+    ops_sync, publish_entry<ArpDevice, halo_arp_table>, destroy<ArpDevice, halo_arp_table>, ops_lookup, ops_encap, ops_gather,
+    ops_mark};
 
 }  // namespace
 

@@ -317,6 +317,16 @@ extern "C" HALO_API int halo_arp_encap_via_device(const halo_arp_table_t* t, uin
                : HALO_E_NODEV;
 }
 
+extern "C" HALO_API int halo_arp_loopback_mark_device(const halo_arp_table_t* t, const halo_rx_result_t* d_records,
+                                                      uint32_t n, const uint32_t* d_route_ids, uint32_t in_netif,
+                                                      const halo_pmflow_via_t* d_via, uint8_t* d_mark,
+                                                      halo_stream_t stream) {
+    if (!t) return HALO_E_INVAL;
+    if (in_netif >= t->cfg.n_netifs) return HALO_E_RANGE;
+    const DeviceOps* ops = device_ops ? device_ops() : nullptr;
+    return ops ? ops->mark(t, d_records, n, d_route_ids, in_netif, d_via, d_mark, stream) : HALO_E_NODEV;
+}
+
 extern "C" HALO_API uint64_t halo_arp_gather_workspace(uint32_t n) {
     const uint64_t tiles = ((uint64_t)n + kGatherTile - 1) / kGatherTile;
     return 4 * (tiles ? tiles : 1);  // one u32 per tile

@@ -88,6 +88,8 @@ struct DeviceOps {
     int (*gather)(const uint8_t* d_bytes, const uint32_t* d_offsets_dw, const uint16_t* d_lens,
                   const halo_rx_result_t* d_records, uint32_t n, uint32_t netif, halo_arp_msg_t* d_msgs, uint32_t cap,
                   uint32_t* d_count, void* d_workspace, uint64_t workspace_bytes, halo_stream_t stream);
+    int (*mark)(const halo_arp_table* t, const halo_rx_result_t* d_records, uint32_t n, const uint32_t* d_route_ids,
+                uint32_t in_netif, const halo_pmflow_via_t* d_via, uint8_t* d_mark, halo_stream_t stream);
 };
 // Defined by arp_fwd.hip; absent (null) in a host-only build, where the device calls are HALO_E_NODEV.
 const DeviceOps* device_ops() __attribute__((weak));

@@ -191,20 +191,28 @@ class ReturnFlows:
     """``forward_return_flows``' result: ``records``, ``route_ids``, ``ops``, ``via``, ``hit``,
     ``pm_counts``, the out NetIf's ``nat_verdict`` / ``nat_ref`` / ``nat_miss`` (None without a NAT
     table), ``fixup_result`` and the encap's ``results`` / ``counts`` / ``miss_count`` — what
-    ``egress_arp(data, offsets_dw, lens, results, ...)`` takes."""
+    ``egress_arp(data, offsets_dw, lens, results, ...)`` takes — and ``mark`` (``loopback.mark``'s, None
+    without ``loopback=True``)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
 
 
 def forward_return_flows(data, offsets_dw, lens, *, netif, in_netif: int, now: int, pmflow, routes, arp, nat=None,
-                         records=None, steps: int = TX_TTL, check_sum_enable: bool = True, stream=None) -> ReturnFlows:
+                         records=None, steps: int = TX_TTL, check_sum_enable: bool = True, stream=None,
+                         loopback: bool = False) -> ReturnFlows:
     """The forward chain for a batch a non-NAT NetIf received (cuda tensors as ``parse_frames_batch``),
     rewritten in place: parse (unless ``records`` is given) -> ``routes.FindRouteRecords`` ->
     ``pmflow.lookup`` -> ``nat.lookup_lan`` with the return-flow hits skipped (``nat``: the NAT table
     of the NetIf the routes point at, or None) -> fixup (TTL, then the SNAT the lookups chose) ->
     ``arp.encap_via`` for the frames whose TTL survived. No host round trip. A ``nat`` MISS (a new
-    flow) keeps the caller's slow path, ``NatTable.resolve_misses``, as before."""
+    flow) keeps the caller's slow path, ``NatTable.resolve_misses``, as before.
+
+    ``loopback=True`` puts ``loopback.mark`` between ``pmflow.lookup`` and ``nat.lookup_lan``: a packet
+    addressed to the out NetIf's own address is skipped by the NAT lookup as the return-flow hits are
+    (the reference returns at :201, ahead of :203-225), so it reaches the encap's LOOPBACK verdict
+    with its LAN source and no flow is added for it. The result then carries ``mark``; ``loopback.gather``
+    takes ``results`` as it stands."""
     import torch
 
     from . import protocol
@@ -218,8 +226,14 @@ def forward_return_flows(data, offsets_dw, lens, *, netif, in_netif: int, now: i
     ops[:, 0] = steps  # the steps every frame takes (HALO_TX_TTL; callers add HALO_TX_RECALC / _DPDK_FILL)
     ops, via, hit, pm_counts = pmflow.lookup(records, now, route_ids, ops=ops, stream=stream)
     nat_verdict = nat_ref = nat_miss = None
+    lo_mark, skip = None, hit
+    if loopback:
+        from . import loopback as lo
+
+        lo_mark = lo.mark(arp, records, route_ids, in_netif, via=via, stream=stream)
+        skip = hit | lo_mark
     if nat is not None:
-        ops, nat_verdict, nat_ref, nat_miss = nat.lookup_lan(records, now, ops=ops, skip=hit, stream=stream)
+        ops, nat_verdict, nat_ref, nat_miss = nat.lookup_lan(records, now, ops=ops, skip=skip, stream=stream)
     fixup_result = torch.zeros(n, dtype=torch.uint8, device=data.device)
     protocol.tx_fixup_batch(data, offsets_dw, lens, ops.reshape(-1), check_sum_enable=check_sum_enable,
                             result=fixup_result, stream=stream)
@@ -228,4 +242,4 @@ def forward_return_flows(data, offsets_dw, lens, *, netif, in_netif: int, now: i
                                                 stream=stream)
     return ReturnFlows(records=records, route_ids=route_ids, ops=ops, via=via, hit=hit, pm_counts=pm_counts,
                        nat_verdict=nat_verdict, nat_ref=nat_ref, nat_miss=nat_miss, fixup_result=fixup_result,
-                       alive=alive, results=results, counts=counts, miss_count=miss_count)
+                       alive=alive, results=results, counts=counts, miss_count=miss_count, mark=lo_mark)

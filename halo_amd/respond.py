@@ -174,20 +174,21 @@ class Replies:
 
 def build_replies(data, offsets_dw, lens, records, *, netif, self_netif: int, builder, routes, arp, nat_verdict=None,
                   ops=None, fixup_result=None, tcp_ports=None, cap: int | None = None, out_stride: int = 128,
-                  check_sum_enable: bool = True, stream=None) -> Replies:
+                  check_sum_enable: bool = True, stream=None, l3_start: bool = False) -> Replies:
     """respond -> ``builder.build`` with the rx batch ``data`` as payload -> ``routes.FindRoute`` of
     the replies' destinations -> ``arp.encap_tx``. Slot k of ``frames`` (``out_stride`` bytes, a
     multiple of 4) holds reply k; slots at and beyond the reply count are masked out (``select``), so
     the whole chain runs without a host round trip. Every reply is built (and takes its iphId)
     before the route and ARP verdicts drop any. ``builder`` is a ``TxBuilder`` for at least ``cap``
-    frames, ``routes`` a synced ``RouteTable``, ``arp`` an ``ArpTable`` synced with it."""
+    frames, ``routes`` a synced ``RouteTable``, ``arp`` an ``ArpTable`` synced with it. ``l3_start``: the
+    batch is a NetIf's LoChan packets (``loopback.drain``), every buffer starting at its IPv4 header."""
     import torch
 
     assert out_stride % 4 == 0 and out_stride >= 60
     n = int(lens.shape[0])
     cap = n if cap is None else cap
     r = respond(offsets_dw, lens, records, netif=netif, nat_verdict=nat_verdict, ops=ops, fixup_result=fixup_result,
-                tcp_ports=tcp_ports, cap=cap, stream=stream)
+                tcp_ports=tcp_ports, cap=cap, l3_start=l3_start, stream=stream)
     dev = data.device
     slots = max(cap, 1)
     # a slot at or beyond the count keeps the zeroed descriptor: proto 0 is HALO_TX_B_PROTO, not built, length 0

@@ -973,7 +973,8 @@ HALO_API int halo_switch_debug_set_epoch(halo_switch_t* sw, uint32_t epoch);
  * Locally originated packets take TxIpv4's variant of the step, halo_arp_encap_tx_device, on the
  * frames halo_tx_build_batch_device built ("local responders" below).
  * Not covered: Router.Ipv4PktFwdHook; compact records in the gather (DHCP: its own section below);
- * UDP service replies (the handlers' job); sending the LoChan copy of a LOOPBACK. */
+ * UDP service replies (the handlers' job). The LoChan copy of a LOOPBACK: halo_lo_gather_device
+ * ("loopback" below). */
 typedef struct halo_arp_table halo_arp_table_t;
 #define HALO_ARP_MAX_NETIFS 64u
 #define HALO_ARP_AGE 300u          /* SetArpCache: ExpTime = now + 300             */
@@ -1019,7 +1020,7 @@ typedef struct halo_arp_msg { /* one received ARP message, as halo_arp_gather_de
 #define HALO_ARP_V_NO_ROUTE 1u    /* HALO_ROUTE_NONE                                               */
 #define HALO_ARP_V_ROUTE_PANIC 2u /* HALO_ROUTE_PANIC                                              */
 #define HALO_ARP_V_LOOPBACK 3u    /* dst == the out NetIf's IpAddr, in NetIf not NATing (:180-201);
-                                     the LoChan copy is the caller's                               */
+                                     the LoChan copy: halo_lo_gather_device ("loopback")          */
 #define HALO_ARP_V_OWN_IP 4u      /* GetArpCache(own IpAddr): nil, no request                      */
 #define HALO_ARP_V_MISS 5u        /* nil: the packet is dropped, one SendArpReq(target_ip) is owed */
 #define HALO_ARP_V_HIT 6u         /* the frame's bytes 0-11 were rewritten                         */
@@ -1115,7 +1116,7 @@ HALO_API int halo_arp_encap_device(const halo_arp_table_t* t, uint8_t* d_bytes, 
  *     out_netif = self_netif, bytes 0-5 = ff x 6, bytes 6-11 = netif[self_netif].mac, tx_len =
  *     max(len, 60), target_ip = 0 (:60-61, :85-86, :92-93);
  *   otherwise dst == netif[out].ip -> LOOPBACK whatever nat_enable says (:71-80). The LoChan copy,
- *     exactly totalLen bytes from byte 14, stays the caller's.
+ *     exactly totalLen bytes from byte 14, is halo_lo_gather_device's with HALO_LO_TX ("loopback").
  * Everything else is unchanged: NONE (also a slot that was not built: length 0), NO_ROUTE,
  * ROUTE_PANIC, OWN_IP, MISS, HIT and the exact bytes written. HALO_E_RANGE: self_netif >= n_netifs. */
 HALO_API int halo_arp_encap_tx_device(const halo_arp_table_t* t, uint8_t* d_bytes, const uint32_t* d_offsets_dw,
@@ -1412,6 +1413,99 @@ HALO_API int halo_tx_egress_host(const halo_egress_config_t* cfg, uint32_t kind,
 HALO_API int halo_ring_write_span(void* ring_memory, const uint8_t* span, uint64_t span_bytes,
                                   uint32_t* records_written, uint64_t* bytes_written);
 
+/* ---- loopback: LoChan packet streams from a decided batch ------------------------------------
+ * The producer side of a NetIf's LoChan. Ipv4RouteForward copies a packet whose destination is the
+ * out NetIf's own address (in NetIf not NATing) into that NetIf's LoChan and returns before the
+ * SNAT step (engine/ipv4_engine.go:193-201, ahead of :203-225); TxIpv4 does the same for a locally
+ * built packet (:71-80). PacketHandle drains the channel through ParseIpv4Pkt, the own-address
+ * filter and the local Rx{Icmp,Udp,Tcp} (engine/engine.go:353-381): HALO_RX_L3_START parsing,
+ * halo_rx_dispatch_loopback, the responders and local delivery under HALO_RX_L3_START.
+ *
+ * Two calls:
+ *   halo_arp_loopback_mark_device  the encap's LOOPBACK test alone, from records, ahead of the NAT
+ *       lookup: its mark is the d_skip of halo_nat_lookup_lan_device (OR'd with the return-flow
+ *       hits), so a LoChan packet keeps its source and no NatAddFlow runs for it.
+ *   halo_lo_gather_device / _host  after the encap in stream order: a stable multi-way partition of
+ *       the batch's LOOPBACK frames into one L3 batch per out NetIf, in ascending frame index — the
+ *       order in which the in NetIf's goroutine sends to each channel.
+ *
+ * MARK: d_mark[i] is SET to 1 iff ip_proto != 0xFF, and the route id is inside the uploaded array
+ *   or d_via[i] (optional) says HALO_PMFLOW_V_OVERRIDE, and the out NetIf (the route's, or the
+ *   via's) is below n_netifs, and record.dst_ip == netif[out].ip, and netif[in_netif].nat_enable
+ *   == 0; else to 0, for every i < n. No frame byte is touched. For a non-NAT in NetIf nothing
+ *   rewrites bytes 30-33 before the encap, so the mark equals (verdict == LOOPBACK) for every frame
+ *   the encap selects. Records 16-byte aligned, route ids 4, via 8. HALO_E_INVAL before the first
+ *   sync and when the last sync had routes == NULL; HALO_E_RANGE: in_netif >= n_netifs. n == 0 is OK.
+ *
+ * GATHER, which frames: verdict == HALO_ARP_V_LOOPBACK and out_netif < n_netifs.
+ *   forward mode (flags without HALO_LO_TX, after halo_arp_encap_device / _via_device): the packet
+ *     is bytes [14, len) of the frame as they are now — the whole ethPayload, Ethernet padding
+ *     included, TTL already decremented (:134 runs before :195). pkt_len = len - 14. SENDABLE:
+ *     34 <= len <= 1514 (9014 with HALO_RX_JUMBO_EXT).
+ *   tx mode (HALO_LO_TX, after halo_arp_encap_tx_device): the packet is exactly totalLen bytes from
+ *     byte 14, totalLen = big-endian frame bytes 16-17 (:76-78). SENDABLE: 20 <= totalLen <= len - 14.
+ *   A selected frame that is not sendable goes nowhere and is counted once in *d_skipped (optional,
+ *   INCREMENTED).
+ * LAYOUT: NetIf p's packets start at d_out + p * region_bytes; each packet starts on a 4-byte
+ *   boundary and is followed by zeros up to the next one: size = (pkt_len + 3) & ~3.
+ * PER-PACKET ARRAYS, index_cap entries per NetIf, for k < min(frames, index_cap):
+ *   d_pkt_off_dw[p * index_cap + k]  the packet's dword offset from its NetIf's region start, or
+ *                                    0xFFFFFFFF beyond the written prefix
+ *   d_pkt_len[p * index_cap + k]     pkt_len
+ *   d_index[p * index_cap + k]       the source frame index
+ *   so that (d_out + p * region_bytes, d_pkt_off_dw + p * index_cap, d_pkt_len + p * index_cap) with
+ *   n = min(frames_written, index_cap) is what a HALO_RX_L3_START parse takes, as it lies.
+ * SUMMARIES: one halo_egress_port_t per NetIf, SET, with egress's meaning: frames / bytes are the
+ *   totals, frames_written / bytes_written the prefix that fits.
+ * REGION OVERFLOW (build-defined): the egress rule. NetIf p's packets are written while they fit
+ *   wholly in region_bytes; the first that does not fit ends the NetIf's written prefix, and the
+ *   totals are still reported so that the caller can resubmit the tail. (The reference's channel
+ *   holds 1,024 packets and blocks the sender when full, engine/engine.go:209; blocking has no
+ *   batch meaning.)
+ * READS: nothing of a frame that is not selected and — forward mode — sendable (tx mode reads the
+ *   dword with bytes 16-19 of a selected frame of at least 34 bytes to learn totalLen); nothing past
+ *   the 4-byte word that holds the packet's last byte, and the bytes of that word beyond the packet
+ *   do not reach the output. The batch is never written.
+ * WRITES: exactly [p * region_bytes, p * region_bytes + bytes_written) of each NetIf, the n_netifs
+ *   summaries, the array entries above, *d_skipped; nothing else.
+ * The device call is asynchronous on `stream` with no host round trip: three launches (per-tile
+ * counts, a scan over tiles, the scatter). n == 0 is OK and zeroes the summaries. Every argument is
+ * checked before any device call. HALO_E_INVAL: a null cfg / d_ports, a null array with n > 0,
+ * n_netifs outside 1..64, flags other than HALO_RX_JUMBO_EXT | HALO_LO_TX, region_bytes not a
+ * multiple of 16 or above 2^34, d_out null with region_bytes > 0 or not 16-byte aligned, any of the
+ * three per-packet arrays null with index_cap > 0, a misaligned array (offsets, pkt_off, index,
+ * skipped: 4; lens, pkt_len: 2; results, summaries, workspace: 8), workspace_bytes <
+ * halo_lo_gather_workspace(n, n_netifs). HALO_E_NODEV / _ARCH as elsewhere.
+ * Not covered: Router.Ipv4PktFwdHook; a blocking channel; compact records in the mark; a loopback
+ * step in the engine loop's NetIf. */
+#define HALO_LO_TX 0x100u /* halo_lo_config_t.flags: tx mode, packets are totalLen bytes */
+typedef struct halo_lo_config {
+    uint32_t n_netifs;     /* 1..64                                                                  */
+    uint32_t flags;        /* HALO_RX_JUMBO_EXT (forward mode's cap), HALO_LO_TX                     */
+    uint64_t region_bytes; /* NetIf p's packets start at d_out + p * region_bytes; a multiple of 16
+                              for the device call; at most 2^34                                      */
+    uint32_t index_cap;    /* entries per NetIf in each of the three per-packet arrays               */
+    uint32_t reserved;     /* 0                                                                      */
+} halo_lo_config_t;        /* 24 B */
+HALO_API int halo_arp_loopback_mark_device(const halo_arp_table_t* t, const halo_rx_result_t* d_records, uint32_t n,
+                                           const uint32_t* d_route_ids, uint32_t in_netif,
+                                           const halo_pmflow_via_t* d_via, uint8_t* d_mark, halo_stream_t stream);
+/* Bytes of device workspace (8-byte aligned) a call over n frames and n_netifs NetIfs needs; 0 for
+ * n_netifs outside 1..64. One workspace serves any number of calls issued on one stream. */
+HALO_API uint64_t halo_lo_gather_workspace(uint32_t n, uint32_t n_netifs);
+HALO_API int halo_lo_gather_device(const halo_lo_config_t* cfg, const uint8_t* d_bytes, const uint32_t* d_offsets_dw,
+                                   const uint16_t* d_lens, uint32_t n, const halo_arp_result_t* d_results,
+                                   uint8_t* d_out, halo_egress_port_t* d_ports, uint32_t* d_pkt_off_dw,
+                                   uint16_t* d_pkt_len, uint32_t* d_index, uint32_t* d_skipped, void* d_workspace,
+                                   uint64_t workspace_bytes, halo_stream_t stream);
+/* The same outputs from the sequential loop over host memory; no HIP. The caller picks it by name
+ * for polls at the reference's cadence. `out` needs no alignment and region_bytes may be any value
+ * up to 2^34 here. */
+HALO_API int halo_lo_gather_host(const halo_lo_config_t* cfg, const uint8_t* bytes, const uint32_t* offsets_dw,
+                                 const uint16_t* lens, uint32_t n, const halo_arp_result_t* results, uint8_t* out,
+                                 halo_egress_port_t* ports, uint32_t* pkt_off_dw, uint16_t* pkt_len, uint32_t* index,
+                                 uint32_t* skipped);
+
 /* ---- the tx ring producer: halo_ring_write_span from device memory ---------------------------
  * An egress stream (halo_tx_egress_*_device) is published into its tx ring where it lies in HBM:
  * the device finds the record boundaries, reads head and tail, copies the records that fit into the
@@ -1574,7 +1668,7 @@ HALO_API int halo_rx_dispatch_loopback(const halo_rx_result_t* results, uint32_t
  * OWN_IP has still consumed its iphId (BuildIpv4Pkt runs before FindRoute): build every descriptor,
  * drop afterwards.
  * Not covered: Router.Ipv4PktFwdHook; UDP service replies (the
- * handlers' job); sending the LoChan copy of a LOOPBACK reply.
+ * handlers' job). The LoChan copy of a LOOPBACK reply: halo_lo_gather_device with HALO_LO_TX.
  * The device call: three launches on `stream` (tile counts, scan, scatter), every argument checked
  * before a device is looked for. Alignment: d_records 16; d_desc, d_src 8; offsets, ops, ports map,
  * dst_ip, count, kind counts, workspace 4; lens 2. HALO_E_INVAL: null netif / d_count, a null
