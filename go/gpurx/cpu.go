@@ -26,7 +26,8 @@ func ParseFramesCPU(buf []byte, off []uint64, lens []uint16, netif *NetIfCfg, l3
 		return nil
 	}
 	for i, o := range off {
-		if o+uint64(lens[i]) > uint64(len(buf)) {
+		// offset first, then length against what is left: o + len wraps past 2^64
+		if o > uint64(len(buf)) || uint64(lens[i]) > uint64(len(buf))-o {
 			return errors.New("gpurx: a frame reaches past the end of buf")
 		}
 	}

@@ -45,7 +45,9 @@ def parse_frames_cpu(data: np.ndarray, offsets: np.ndarray, lens: np.ndarray, *,
     n = int(lens.shape[0])
     if offsets.shape[0] != n:
         raise ValueError("offsets and lens differ in length")
-    if n and int((offsets + lens).max()) > data.nbytes:
+    # offset first, then length against what is left: offsets + lens is u64 arithmetic and wraps
+    nbytes = np.uint64(data.nbytes)
+    if n and ((offsets > nbytes).any() or (lens > nbytes - np.minimum(offsets, nbytes)).any()):
         raise ValueError("a frame reaches past the end of data")
     rec = RECORD16_DTYPE if compact else RESULT_DTYPE
     if out is None:

@@ -188,6 +188,21 @@ def test_argument_checks(cpu):
     assert out["status"][0] == 2  # all-zero frame: EtherType 0 is not whitelisted
 
 
+def test_wrapper_bounds_check_does_not_wrap(cpu):
+    """parse_frames_cpu's own bounds check is done without a u64 sum: offset 2^64 - 8 with length 16
+    sums to 8 and once passed; it, an offset just past the end and a length just past what is left
+    are ValueError, and a frame that ends exactly at the buffer's end parses."""
+    from halo_amd._lib import NetIf
+
+    buf = np.zeros(64, np.uint8)
+    ni = NetIf.make()
+    for off, ln in ((2**64 - 8, 16), (2**64 - 1, 1), (65, 0), (60, 5), (0, 65)):
+        with pytest.raises(ValueError):
+            cpu.parse_frames_cpu(buf, np.array([0, off], np.uint64), np.array([64, ln], np.uint16), netif=ni)
+    got = cpu.parse_frames_cpu(buf, np.array([0, 64, 4], np.uint64), np.array([64, 0, 60], np.uint16), netif=ni)
+    assert list(got["status"]) == [2, 1, 2]
+
+
 _READ_CONTRACT = r"""
 import ctypes, mmap, sys
 import numpy as np
