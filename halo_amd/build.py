@@ -24,7 +24,7 @@ BENCH_OUT = os.path.join(ROOT, "tools", "libhalo_bench.so")
 CPU_SRC = os.path.join(CSRC, "rx_cpu.cc")
 CPU_OUT = os.path.join(ROOT, "halo_amd", "lib", "libhalo_rx_cpu.so")
 HEADERS = ["halo_common.h", "halo_limits.h", "host_logic.h", "device_util.h", "flow_key.h", "flow_table.h", "nat_table.h", "switch_table.h", "arp_table.h", "tx_egress.h",
-           "tx_respond.h", "tx_ring.h", "rx_deliver.h", "rx_kcp.h", "tx_kcp.h", "rx_dhcp.h", "dhcp_table.h", "lo_gather.h", "kcp_check_host.h", "kcp_crc_device.h", "pmflow_table.h", "rx_dispatch.h", "route_view.h", "tile_scan.h", "stream_scan.h", "rx_frame.h", "rx_hist.h", "rx_launch.h", "host_layout.h", "device_table.h", os.path.join("..", "..", "include", "halo_rx.h")]
+           "tx_respond.h", "tx_ring.h", "rx_deliver.h", "rx_kcp.h", "tx_kcp.h", "rx_dhcp.h", "dhcp_table.h", "lo_gather.h", "kcp_check_host.h", "kcp_crc_device.h", "pmflow_table.h", "rx_dispatch.h", "route_view.h", "tile_scan.h", "stream_scan.h", "port_streams.h", "rx_frame.h", "rx_hist.h", "rx_launch.h", "host_layout.h", "device_table.h", os.path.join("..", "..", "include", "halo_rx.h")]
 
 
 def _hipcc() -> str:

@@ -1,7 +1,8 @@
 // lo_gather.h — the loopback step (include/halo_rx.h, "loopback"): the selection and layout
 // arithmetic the host loop (lo_gather_host.cc) and the kernels (lo_gather.hip) must agree on — which
 // ARP result selects a frame, a packet's length in either mode, which packets are sendable, a
-// packet's size in its NetIf's region — and the workspace layout. Plain C++17, no HIP:
+// packet's size in its NetIf's region; the workspace layout and the argument checks it has in common
+// with the egress step are host_layout.h's. Plain C++17, no HIP:
 // lo_gather_host.cc compiles alone with g++ (tools/fuzz_lo.cc drives it under ASan/UBSan) and into
 // libhalo_rx.so.
 #pragma once

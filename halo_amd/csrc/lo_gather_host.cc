@@ -11,25 +11,17 @@ namespace halo {
 namespace lo {
 namespace {
 
-// What both entry points ask of cfg, the batch and the outputs
+// What both entry points ask of cfg, the batch and the outputs: host_layout.h's checks of a
+// per-port stream call and the three per-packet arrays
 int check_args(const halo_lo_config_t* cfg, uintptr_t out_align, const uint8_t* bytes, const uint32_t* offsets_dw,
                const uint16_t* lens, uint32_t n, const halo_arp_result_t* results, const uint8_t* out,
                const halo_egress_port_t* ports, const uint32_t* pkt_off_dw, const uint16_t* pkt_len, const uint32_t* index,
                const uint32_t* skipped) {
-    if (!cfg || !ports) return HALO_E_INVAL;
-    if (cfg->n_netifs < 1 || cfg->n_netifs > HALO_ARP_MAX_NETIFS) return HALO_E_INVAL;
-    if (cfg->flags & ~(HALO_RX_JUMBO_EXT | HALO_LO_TX)) return HALO_E_INVAL;
-    // a device region starts 16-byte aligned (the output's alignment); the host loop needs no
-    // alignment. A packet's offset is a u32 of dwords from its region's start.
-    if ((cfg->region_bytes & (out_align - 1)) || cfg->region_bytes > (1ull << 34)) return HALO_E_INVAL;
-    if ((cfg->region_bytes && !out) || misaligned(out, out_align)) return HALO_E_INVAL;
-    if (cfg->index_cap && (!pkt_off_dw || !pkt_len || !index)) return HALO_E_INVAL;
-    if (misaligned(ports, 8) || misaligned(pkt_off_dw, 4) || misaligned(pkt_len, 2) || misaligned(index, 4) ||
-        misaligned(skipped, 4))
-        return HALO_E_INVAL;
-    if (n && (!bytes || !offsets_dw || !lens || !results)) return HALO_E_INVAL;
-    if (misaligned(bytes, 4) || misaligned(offsets_dw, 4) || misaligned(lens, 2) || misaligned(results, 8)) return HALO_E_INVAL;
-    return HALO_OK;
+    if (!cfg || (cfg->index_cap && (!pkt_off_dw || !pkt_len || !index))) return HALO_E_INVAL;
+    if (misaligned(pkt_off_dw, 4) || misaligned(pkt_len, 2) || misaligned(results, 8)) return HALO_E_INVAL;
+    // a region's bound: a packet's offset is a u32 of dwords from its region's start
+    return check_port_stream_args(cfg->n_netifs, HALO_ARP_MAX_NETIFS, cfg->flags, HALO_RX_JUMBO_EXT | HALO_LO_TX, cfg->region_bytes,
+                                  1ull << 34, out, out_align, ports, index, skipped, bytes, offsets_dw, lens, n, results);
 }
 
 }  // namespace
@@ -39,12 +31,10 @@ int check_args(const halo_lo_config_t* cfg, uintptr_t out_align, const uint8_t* 
 using namespace halo;  // host_layout.h
 using namespace halo::lo;
 
-// Workspace of a device call, as the egress step's: per NetIf and tile a u64 byte base, then a u32
-// packet count that the scan turns into the rank base, then a u32 byte count. NetIf p's tiles are
-// contiguous.
+// Workspace of a device call: host_layout.h's, for tiles of kTile frames
 extern "C" HALO_API uint64_t halo_lo_gather_workspace(uint32_t n, uint32_t n_netifs) {
     if (n_netifs < 1 || n_netifs > HALO_ARP_MAX_NETIFS) return 0;
-    return 16ull * tiles_of(n, kTile) * n_netifs;
+    return port_stream_workspace(n, kTile, n_netifs);
 }
 
 extern "C" HALO_API int halo_lo_gather_device(const halo_lo_config_t* cfg, const uint8_t* d_bytes,

@@ -1,9 +1,10 @@
-// stream_scan.h — what the stream stages share on the device (tx_egress.hip: a stream of ring
-// records per port; rx_deliver.hip: one of delivery records; a stream's region takes the longest
-// prefix of whole records that fits): the one-workgroup scan of the tiles' record counts and bytes
-// together, which finds the tile the region's cut falls in, and the count kernels' wave sum. On
-// top of tile_scan.h. gfx950 only. (The scatter's fit bookkeeping and copy loop stay in the two
-// files: DESIGN.md §22.1.)
+// stream_scan.h — what the stream stages share on the device (port_streams.h: a stream per port,
+// of ring records for tx_egress.hip and of L3 packets for lo_gather.hip; rx_deliver.hip: one of
+// delivery records; a stream's region takes the longest prefix of whole records that fits): the
+// one-workgroup scan of the tiles' record counts and bytes together, which finds the tile the
+// region's cut falls in, and the count kernels' wave sum. On top of tile_scan.h. gfx950 only.
+// (The scatter's fit bookkeeping and copy loop stay in port_streams.h and rx_deliver.hip:
+// DESIGN.md §22.1, §22.4.)
 #pragma once
 #include <stddef.h>
 

@@ -1,7 +1,7 @@
 // tx_egress.h — the egress step (include/halo_rx.h, "egress"): the layout arithmetic the host loop
 // (tx_egress_host.cc) and the kernels (tx_egress.hip) must agree on — tx_len, record size, which
-// frames are sendable, how each kind's selector becomes a port mask — and the workspace layout.
-// Plain C++17, no HIP: tx_egress_host.cc compiles alone with g++ (tools/fuzz_egress.cc drives it
+// frames are sendable, how each kind's selector becomes a port mask; the workspace layout and the
+// argument checks it has in common with the loopback step are host_layout.h's. Plain C++17, no HIP: tx_egress_host.cc compiles alone with g++ (tools/fuzz_egress.cc drives it
 // under ASan/UBSan) and into libhalo_rx.so.
 #pragma once
 #if defined(__HIPCC__)

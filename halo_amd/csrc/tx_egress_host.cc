@@ -11,35 +11,23 @@ namespace halo {
 namespace egress {
 namespace {
 
-// What all four entry points ask of cfg and the outputs
-int check_common(const halo_egress_config_t* cfg, const void* out, uintptr_t out_align, const halo_egress_port_t* ports,
-                 const uint32_t* index, const uint32_t* skipped) {
-    if (!cfg || !ports) return HALO_E_INVAL;
-    if (cfg->n_ports < 1 || cfg->n_ports > HALO_EGRESS_MAX_PORTS) return HALO_E_INVAL;
-    if (cfg->flags & ~HALO_RX_JUMBO_EXT) return HALO_E_INVAL;
-    // a device region starts 16-byte aligned (the output's alignment); the host loop needs no alignment
-    if ((cfg->region_bytes & (out_align - 1)) || cfg->region_bytes > (1ull << 56)) return HALO_E_INVAL;
-    if ((cfg->region_bytes && !out) || misaligned(out, out_align)) return HALO_E_INVAL;
-    if (cfg->index_cap && !index) return HALO_E_INVAL;
-    if (misaligned(ports, 8) || misaligned(index, 4) || misaligned(skipped, 4)) return HALO_E_INVAL;
-    return HALO_OK;
-}
-
-int check_batch(const uint8_t* bytes, const uint32_t* offsets_dw, const uint16_t* lens, uint32_t n, const void* selectors,
-                uintptr_t selector_align) {
-    if (n && (!bytes || !offsets_dw || !lens || !selectors)) return HALO_E_INVAL;
-    if (misaligned(bytes, 4) || misaligned(offsets_dw, 4) || misaligned(lens, 2) || misaligned(selectors, selector_align))
-        return HALO_E_INVAL;
-    return HALO_OK;
+// What all four entry points ask of cfg, the batch and the outputs: host_layout.h's checks of a
+// per-port stream call, the index list and the selectors' alignment by kind
+int check_args(const halo_egress_config_t* cfg, const void* out, uintptr_t out_align, const halo_egress_port_t* ports,
+               const uint32_t* index, const uint32_t* skipped, const uint8_t* bytes, const uint32_t* offsets_dw,
+               const uint16_t* lens, uint32_t n, const void* selectors, uintptr_t selector_align) {
+    if (!cfg || (cfg->index_cap && !index) || misaligned(selectors, selector_align)) return HALO_E_INVAL;
+    return check_port_stream_args(cfg->n_ports, HALO_EGRESS_MAX_PORTS, cfg->flags, HALO_RX_JUMBO_EXT, cfg->region_bytes,
+                                  1ull << 56, out, out_align, ports, index, skipped, bytes, offsets_dw, lens, n, selectors);
 }
 
 int device_call(const halo_egress_config_t* cfg, uint32_t kind, uintptr_t selector_align, const uint8_t* d_bytes,
                 const uint32_t* d_offsets_dw, const uint16_t* d_lens, uint32_t n, const void* d_selectors,
                 uint64_t flood_mask, uint8_t* d_out, halo_egress_port_t* d_ports, uint32_t* d_index, uint32_t* d_skipped,
                 void* d_workspace, uint64_t workspace_bytes, halo_stream_t stream) {
-    int rc;
-    if ((rc = check_common(cfg, d_out, 16, d_ports, d_index, d_skipped))) return rc;
-    if ((rc = check_batch(d_bytes, d_offsets_dw, d_lens, n, d_selectors, selector_align))) return rc;
+    const int rc = check_args(cfg, d_out, 16, d_ports, d_index, d_skipped, d_bytes, d_offsets_dw, d_lens, n, d_selectors,
+                              selector_align);
+    if (rc) return rc;
     if (n && (!d_workspace || workspace_bytes < halo_tx_egress_workspace(n, cfg->n_ports))) return HALO_E_INVAL;
     if (misaligned(d_workspace, 8)) return HALO_E_INVAL;
     const DeviceOps* ops = device_ops ? device_ops() : nullptr;
@@ -55,11 +43,10 @@ int device_call(const halo_egress_config_t* cfg, uint32_t kind, uintptr_t select
 using namespace halo;  // host_layout.h
 using namespace halo::egress;
 
-// Workspace of a device call: per port and tile a u64 byte base, then a u32 record count that the
-// scan turns into the rank base, then a u32 byte count. Column-major: port p's tiles are contiguous.
+// Workspace of a device call: host_layout.h's, for tiles of kTile frames
 extern "C" HALO_API uint64_t halo_tx_egress_workspace(uint32_t n, uint32_t n_ports) {
     if (n_ports < 1 || n_ports > HALO_EGRESS_MAX_PORTS) return 0;
-    return 16ull * tiles_of(n, kTile) * n_ports;
+    return port_stream_workspace(n, kTile, n_ports);
 }
 
 extern "C" HALO_API int halo_tx_egress_masks_device(const halo_egress_config_t* cfg, const uint8_t* d_bytes,
@@ -95,10 +82,9 @@ extern "C" HALO_API int halo_tx_egress_host(const halo_egress_config_t* cfg, uin
                                             const void* selectors, uint64_t flood_mask, uint8_t* out,
                                             halo_egress_port_t* ports, uint32_t* index, uint32_t* skipped) {
     if (kind > HALO_EGRESS_KIND_SWITCH) return HALO_E_INVAL;
-    int rc;
-    if ((rc = check_common(cfg, out, 1, ports, index, skipped))) return rc;
-    const uintptr_t sel_size = kind == HALO_EGRESS_KIND_SWITCH ? 4 : 8;
-    if ((rc = check_batch(bytes, offsets_dw, lens, n, selectors, sel_size))) return rc;
+    const int rc = check_args(cfg, out, 1, ports, index, skipped, bytes, offsets_dw, lens, n, selectors,
+                              kind == HALO_EGRESS_KIND_SWITCH ? 4 : 8);
+    if (rc) return rc;
     const uint32_t n_ports = cfg->n_ports;
     const uint64_t valid = port_bits(n_ports), region = cfg->region_bytes;
     memset(ports, 0, n_ports * sizeof *ports);

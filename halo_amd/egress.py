@@ -83,6 +83,21 @@ def workspace_bytes(n: int, n_ports: int) -> int:
     return int(_lib.lib.halo_tx_egress_workspace(n, n_ports))
 
 
+def _device_outputs(dev, n_ports, region_bytes, wsb, out, skipped, workspace):
+    """What a per-port stream call on the device (here and in ``loopback.gather``) allocates when not
+    given: (out, the 24-byte summaries, skipped, workspace, the workspace's bytes)."""
+    import torch
+
+    if out is None:
+        out = torch.empty(max(n_ports * region_bytes, 16), dtype=torch.uint8, device=dev)
+    ports = torch.empty((n_ports, 24), dtype=torch.uint8, device=dev)
+    if skipped is None:
+        skipped = torch.zeros(1, dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(max(wsb, 8) // 8, dtype=torch.int64, device=dev)
+    return out, ports, skipped, workspace, workspace.numel() * workspace.element_size()
+
+
 def _device(kind, data, offsets_dw, lens, selectors, n_ports, region_bytes, index_cap, jumbo, flood_mask, out, workspace,
             skipped, stream, index=None):
     import ctypes
@@ -90,19 +105,11 @@ def _device(kind, data, offsets_dw, lens, selectors, n_ports, region_bytes, inde
     import torch
 
     n = int(lens.shape[0])
-    dev = data.device
     cfg = _config(n_ports, region_bytes, index_cap, jumbo)
-    if out is None:
-        out = torch.empty(max(n_ports * region_bytes, 16), dtype=torch.uint8, device=dev)
-    ports = torch.empty((n_ports, 24), dtype=torch.uint8, device=dev)
+    out, ports, skipped, workspace, ws_bytes = _device_outputs(data.device, n_ports, region_bytes, workspace_bytes(n, n_ports),
+                                                               out, skipped, workspace)
     if index is None and index_cap:
-        index = torch.empty((n_ports, index_cap), dtype=torch.int32, device=dev)
-    if skipped is None:
-        skipped = torch.zeros(1, dtype=torch.int32, device=dev)
-    wsb = workspace_bytes(n, n_ports)
-    if workspace is None:
-        workspace = torch.empty(max(wsb, 8) // 8, dtype=torch.int64, device=dev)
-    ws_bytes = workspace.numel() * workspace.element_size()
+        index = torch.empty((n_ports, index_cap), dtype=torch.int32, device=data.device)
     st = (stream if stream is not None else torch.cuda.current_stream()).cuda_stream
     args = [ctypes.byref(cfg), _lib.ptr(data), _lib.ptr(offsets_dw), _lib.ptr(lens), n, _lib.ptr(selectors)]
     if kind == EGRESS_KIND_SWITCH:

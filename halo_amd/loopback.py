@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import EGRESS_PORT_DTYPE, HALO_LO_TX, HALO_RX_JUMBO_EXT, LO_NOT_WRITTEN  # noqa: F401
+from .egress import EgressResult, _device_outputs
 
 
 def packet_size(pkt_len: int) -> int:
@@ -28,32 +29,14 @@ def packet_size(pkt_len: int) -> int:
     return (int(pkt_len) + 3) & ~3
 
 
-class LoResult:
-    """What one gather wrote. ``out`` is the whole output buffer (uint8 [n_netifs * region_bytes]),
-    ``ports_raw`` the summaries, ``pkt_off_dw_raw`` / ``pkt_len_raw`` / ``index_raw`` the per-packet
-    arrays ([n_netifs, index_cap]) and ``skipped`` the counter; device results hold cuda tensors and
-    copy on access."""
+class LoResult(EgressResult):
+    """What one gather wrote: an ``EgressResult`` whose ports are the NetIfs (``out`` is uint8
+    [n_netifs * region_bytes]), with ``pkt_off_dw_raw`` / ``pkt_len_raw`` beside ``index_raw``, the
+    per-packet arrays ([n_netifs, index_cap])."""
 
     def __init__(self, n_netifs, region_bytes, index_cap, out, ports_raw, pkt_off_dw_raw, pkt_len_raw, index_raw, skipped):
-        self.n_netifs, self.region_bytes, self.index_cap = n_netifs, region_bytes, index_cap
-        self.out, self.ports_raw, self.skipped = out, ports_raw, skipped
-        self.pkt_off_dw_raw, self.pkt_len_raw, self.index_raw = pkt_off_dw_raw, pkt_len_raw, index_raw
-        self._ports = None
-
-    @staticmethod
-    def _host(x) -> np.ndarray:
-        return x.cpu().numpy() if hasattr(x, "cpu") else x
-
-    @property
-    def ports(self) -> np.ndarray:
-        """The n_netifs summaries as EGRESS_PORT_DTYPE (synchronises a device result)."""
-        if self._ports is None:
-            self._ports = self._host(self.ports_raw).reshape(-1).view(np.uint8).view(EGRESS_PORT_DTYPE).copy()
-        return self._ports
-
-    @property
-    def n_skipped(self) -> int:
-        return int(self._host(self.skipped).reshape(-1).view(np.uint32)[0])
+        super().__init__(n_netifs, region_bytes, index_cap, out, ports_raw, index_raw, skipped)
+        self.n_netifs, self.pkt_off_dw_raw, self.pkt_len_raw = n_netifs, pkt_off_dw_raw, pkt_len_raw
 
     def n_listed(self, p: int) -> int:
         """Entries of NetIf p in the per-packet arrays: min(frames, index_cap)."""
@@ -70,11 +53,6 @@ class LoResult:
         lo = p * self.region_bytes
         return self.out[lo:lo + self.region_bytes], self.pkt_off_dw_raw[p, :k], self.pkt_len_raw[p, :k]
 
-    def index(self, p: int) -> np.ndarray:
-        """The batch indices of NetIf p's first min(frames, index_cap) packets: uint32."""
-        k = self.n_listed(p)
-        return self._host(self.index_raw[p, :k]).view(np.uint32).copy() if k else np.zeros(0, np.uint32)
-
     def pkt_off_dw(self, p: int) -> np.ndarray:
         k = self.n_listed(p)
         return self._host(self.pkt_off_dw_raw[p, :k]).view(np.uint32).copy() if k else np.zeros(0, np.uint32)
@@ -82,11 +60,6 @@ class LoResult:
     def pkt_len(self, p: int) -> np.ndarray:
         k = self.n_listed(p)
         return self._host(self.pkt_len_raw[p, :k]).view(np.uint16).copy() if k else np.zeros(0, np.uint16)
-
-    def stream(self, p: int) -> np.ndarray:
-        """NetIf p's written bytes: uint8 [bytes_written], host memory."""
-        lo = p * self.region_bytes
-        return np.ascontiguousarray(self._host(self.out[lo:lo + int(self.ports[p]["bytes_written"])]))
 
 
 def _config(n_netifs, region_bytes, index_cap, tx, jumbo):
@@ -128,18 +101,12 @@ def gather(data, offsets_dw, lens, results, n_netifs: int, region_bytes: int, in
     n = int(lens.shape[0])
     dev = data.device
     cfg = _config(n_netifs, region_bytes, index_cap, tx, jumbo)
-    if out is None:
-        out = torch.empty(max(n_netifs * region_bytes, 16), dtype=torch.uint8, device=dev)
-    ports = torch.empty((n_netifs, 24), dtype=torch.uint8, device=dev)
+    out, ports, skipped, workspace, ws_bytes = _device_outputs(dev, n_netifs, region_bytes, workspace_bytes(n, n_netifs), out,
+                                                               skipped, workspace)
     cap = max(index_cap, 1)
     pkt_off = torch.empty((n_netifs, cap), dtype=torch.int32, device=dev)
     pkt_len = torch.empty((n_netifs, cap), dtype=torch.int16, device=dev)
     index = torch.empty((n_netifs, cap), dtype=torch.int32, device=dev)
-    if skipped is None:
-        skipped = torch.zeros(1, dtype=torch.int32, device=dev)
-    if workspace is None:
-        workspace = torch.empty(max(workspace_bytes(n, n_netifs), 8) // 8, dtype=torch.int64, device=dev)
-    ws_bytes = workspace.numel() * workspace.element_size()
     st = (stream if stream is not None else torch.cuda.current_stream()).cuda_stream
     _lib.check("halo_lo_gather_device", _lib.lib.halo_lo_gather_device(
         ctypes.byref(cfg), _lib.ptr(data), _lib.ptr(offsets_dw), _lib.ptr(lens), n, _lib.ptr(results), _lib.ptr(out),

@@ -71,11 +71,11 @@ def switch_batch():
 # ---- past the edges ------------------------------------------------------------------------------
 # edge -> the constants it follows from and the first n past it, as the launch code gives it today
 BOUNDARIES = {
-    "egress_tile": dict(kernels="egress_count_kernel, egress_scatter_kernel: second tile", constants=("kTile",),
+    "egress_tile": dict(kernels="port_count_kernel, port_scatter_kernel of the egress stages: second tile", constants=("kTile",),
                         first_past=257),
-    "egress_scan_pass": dict(kernels="egress_scan_kernel: second pass", constants=("kTile", "kScanPass"),
+    "egress_scan_pass": dict(kernels="port_scan_kernel: second pass", constants=("kTile", "kScanPass"),
                              first_past=262_145),
-    "egress_grid": dict(kernels="egress_count_kernel, egress_scatter_kernel: second trip",
+    "egress_grid": dict(kernels="port_count_kernel, port_scatter_kernel of the egress stages: second trip",
                         constants=("kTile", "egress_blocks"), first_past=524_289),
 }
 
@@ -86,28 +86,42 @@ def _one(pattern: str, text: str) -> str:
     return found[0]
 
 
-def read_constants() -> dict:
-    with open(os.path.join(CSRC, "tx_egress.hip")) as fh:
-        hip = fh.read()
-    with open(os.path.join(CSRC, "tx_egress.h")) as fh:
-        hdr = fh.read()
-    kmax = _one(r"uint32_t egress_blocks\(uint64_t \w+\) \{[^}]*?const uint64_t kMax = ([^;]+);", hip)
+def read_port_streams(stage: str) -> dict:
+    """What tx_egress.hip and lo_gather.hip (`stage`, without suffix) take from port_streams.h: the
+    stage's own kTile pinned to the shared tile, the grid cap of the count and scatter kernels, the
+    scan's pass and a lane's tiles in it. tests/lo_cases.py reads through this too."""
+    def src(name):
+        with open(os.path.join(CSRC, name)) as fh:
+            return fh.read()
+
+    hip, hdr = src(stage + ".hip"), src(stage + ".h")
+    ps, tile, stream = src("port_streams.h"), src("tile_scan.h"), src("stream_scan.h")
+    k_tile = int(_one(r"constexpr uint32_t kTile = (\d+);", hdr))
+    assert k_tile == int(_one(r"constexpr uint32_t kPortTile = (\d+);", ps))
+    _one(r"static_assert\(\w+::kTile == kPortTile &&", hip)
+    kmax = _one(r"uint32_t port_stream_blocks\(uint64_t \w+\) \{[^}]*?const uint64_t kMax = ([^;]+);", ps)
     blocks = 1
     for f in kmax.split("*"):
         blocks *= int(re.fullmatch(r"\s*(\d+)(?:ull|u)?\s*", f).group(1))
-    # egress_scan_kernel calls the streams' fused scan (stream_scan.h), whose one loop advances by
-    # tile_scan.h's pass; the file has no scan loop of its own
-    with open(os.path.join(CSRC, "tile_scan.h")) as fh:
-        tile = fh.read()
-    with open(os.path.join(CSRC, "stream_scan.h")) as fh:
-        stream = fh.read()
-    assert '#include "stream_scan.h"' in hip and "t0 +=" not in hip and "kScanPass =" not in hip + stream
-    _one(r"__global__ void __launch_bounds__\(256\) egress_scan_kernel\([^)]*\) \{[^}]*?=\s*scan_stream_tiles\(", hip)
-    assert len(re.findall(r"scan_stream_tiles\(", hip)) == 1 and '#include "tile_scan.h"' in stream
+    # the stage's kernels are port_streams.h's, launched by its one launch function with that grid;
+    # port_scan_kernel calls the streams' fused scan (stream_scan.h), whose one loop advances by
+    # tile_scan.h's pass, a lane taking consecutive tiles; neither file has a scan loop of its own
+    assert '#include "port_streams.h"' in hip and "<<<" not in hip and len(re.findall(r"launch_port_streams<", hip)) >= 2
+    _one(r"const uint32_t grid = port_stream_blocks\(q\.n_tiles\);\s*port_count_kernel<Stage><<<dim3\(grid\), dim3\(kPortTile\)[^;]*;"
+         r"\s*port_scan_kernel<[^;]*;\s*port_scatter_kernel<Stage><<<dim3\(grid\), dim3\(kPortTile\)", ps)
+    assert '#include "stream_scan.h"' in ps and "t0 +=" not in hip + ps and "kScanPass =" not in hip + ps + stream
+    _one(r"__global__ void __launch_bounds__\(256\) port_scan_kernel\([^)]*\) \{[^}]*?=\s*scan_stream_tiles\(", ps)
+    assert len(re.findall(r"scan_stream_tiles\(", hip + ps)) == 1 and '#include "tile_scan.h"' in stream
     assert _one(r"t0 < n_tiles; t0 \+= (\w+),", stream) == "kScanPass"
-    return {"kTile": int(_one(r"constexpr uint32_t kTile = (\d+);", hdr)),
-            "kScanPass": int(_one(r"constexpr uint32_t kScanPass = (\d+);", tile)),
-            "egress_blocks": blocks}
+    per_lane = int(_one(r"const uint32_t t = t0 \+ (\d+) \* threadIdx\.x;\s*uint32_t c\[", stream))
+    k_pass = int(_one(r"constexpr uint32_t kScanPass = (\d+);", tile))
+    assert k_pass == per_lane * 256
+    return {"kTile": k_tile, "kScanPass": k_pass, "tiles_per_lane": per_lane, "port_stream_blocks": blocks}
+
+
+def read_constants() -> dict:
+    c = read_port_streams("tx_egress")
+    return {"kTile": c["kTile"], "kScanPass": c["kScanPass"], "egress_blocks": c["port_stream_blocks"]}
 
 
 def derived(c: dict) -> dict:

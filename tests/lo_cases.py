@@ -2,20 +2,15 @@
 the seeded corpus of the loopback gather (every length edge against every verdict and every kind of
 out NetIf, packed with garbage in the gaps; in tx mode every relation of totalLen to the frame) and,
 in the manner of tests/scale_cases.py, where the gather's scan changes behaviour with the batch
-size: one lane's tiles, one wave's and one pass, read out of the sources by regular expression so
+size: one lane's tiles, one wave's, one pass and one grid, read out of the sources by regular expression so
 that a moved constant moves the shapes."""
 from __future__ import annotations
-
-import os
-import re
 
 import numpy as np
 
 from tests import arp_cases as K
 from tests import arp_model as AM
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "halo_amd", "csrc")
+from tests import egress_cases as E
 
 ARP_RESULT_DTYPE = np.dtype([("verdict", "u1"), ("out_netif", "u1"), ("tx_len", "<u2"), ("target_ip", "<u4")])
 LENS = [0, 17, 33, 34, 35, 36, 37, 60, 64, 100, 1514, 1515]          # pkt_len % 4 in {0, 1, 2, 3}; both caps
@@ -70,41 +65,25 @@ def region_for(want_bytes: int) -> int:
 # ---- past the edges ------------------------------------------------------------------------------
 # edge -> the constants it follows from and the first n past it, as the sources give it today
 BOUNDARIES = {
-    "lo_scan_lane": dict(kernels="lo_scan_kernel: a second lane of scan_stream_tiles", constants=("kTile", "tiles_per_lane"),
+    "lo_scan_lane": dict(kernels="port_scan_kernel: a second lane of scan_stream_tiles", constants=("kTile", "tiles_per_lane"),
                          first_past=1_025),
-    "lo_scan_wave": dict(kernels="lo_scan_kernel: a second wave", constants=("kTile", "tiles_per_lane"), first_past=65_537),
-    "lo_scan_pass": dict(kernels="lo_scan_kernel: a second pass", constants=("kTile", "kScanPass"), first_past=262_145),
+    "lo_scan_wave": dict(kernels="port_scan_kernel: a second wave", constants=("kTile", "tiles_per_lane"), first_past=65_537),
+    "lo_scan_pass": dict(kernels="port_scan_kernel: a second pass", constants=("kTile", "kScanPass"), first_past=262_145),
+    "lo_grid": dict(kernels="port_count_kernel, port_scatter_kernel of the gather's stages: second trip",
+                    constants=("kTile", "port_stream_blocks"), first_past=524_289),
 }
 
 
-def _one(pattern: str, text: str) -> str:
-    found = re.findall(pattern, text)
-    assert len(found) == 1, (pattern, found)
-    return found[0]
-
-
 def read_constants() -> dict:
-    def src(name):
-        with open(os.path.join(CSRC, name)) as fh:
-            return fh.read()
-
-    hip, hdr, tile, stream = src("lo_gather.hip"), src("lo_gather.h"), src("tile_scan.h"), src("stream_scan.h")
-    # lo_scan_kernel calls the streams' fused scan (stream_scan.h), whose one loop advances by
-    # tile_scan.h's pass, a lane taking consecutive tiles; the file has no scan loop of its own
-    assert '#include "stream_scan.h"' in hip and "t0 +=" not in hip and "kScanPass =" not in hip + stream
-    _one(r"__global__ void __launch_bounds__\(256\) lo_scan_kernel\([^)]*\) \{[^}]*?=\s*scan_stream_tiles\(", hip)
-    assert len(re.findall(r"scan_stream_tiles\(", hip)) == 1 and '#include "tile_scan.h"' in stream
-    assert _one(r"t0 < n_tiles; t0 \+= (\w+),", stream) == "kScanPass"
-    per_lane = int(_one(r"const uint32_t t = t0 \+ (\d+) \* threadIdx\.x;\s*uint32_t c\[", stream))
-    k_pass = int(_one(r"constexpr uint32_t kScanPass = (\d+);", tile))
-    assert k_pass == per_lane * 256
-    return {"kTile": int(_one(r"constexpr uint32_t kTile = (\d+);", hdr)), "kScanPass": k_pass, "tiles_per_lane": per_lane}
+    """The gather's kernels are port_streams.h's: tests/egress_cases.py reads them for both stages."""
+    return E.read_port_streams("lo_gather")
 
 
 def derived(c: dict) -> dict:
     return {"lo_scan_lane": c["kTile"] * c["tiles_per_lane"] + 1,
             "lo_scan_wave": c["kTile"] * c["tiles_per_lane"] * 64 + 1,
-            "lo_scan_pass": c["kTile"] * c["kScanPass"] + 1}
+            "lo_scan_pass": c["kTile"] * c["kScanPass"] + 1,
+            "lo_grid": c["kTile"] * c["port_stream_blocks"] + 1}
 
 
 def past(name: str, r: int) -> int:

@@ -4,7 +4,8 @@ buffer with its 0xA5 sentinel beyond each NetIf's written bytes, the summaries, 
 arrays with their sentinel beyond the written entries, the skip count — and the input left as it
 was. Both modes over the corpus's length / verdict / NetIf mix at the sizes around a wavefront and a
 tile; all frames selected and none; the region cut inside a tile and at a tile's first packet; one
-workspace for two calls; and batches past one lane's tiles, one wave's and one pass of the scan."""
+workspace for two calls; batches past one lane's tiles, one wave's and one pass of the scan; and one
+past one grid of the count and scatter kernels."""
 from __future__ import annotations
 
 import numpy as np
@@ -84,21 +85,26 @@ def _check(r, want: LM.Want, skipped0=7):
 
 
 def _case(dev, frames, data, offs, lens, results, n_netifs, region, index_cap, tx=False, jumbo=False):
-    from halo_amd import loopback as L
-
     want = LM.gather(frames, LM.netifs_of_results(results, n_netifs), n_netifs, region, index_cap, tx, jumbo)
     d, o, ln, res = _up(dev, data, offs, lens, results)
     r = _gather(dev, d, o, ln, res, n_netifs, region, index_cap, tx, jumbo)
     _check(r, want)
     assert np.array_equal(d.cpu().numpy(), data), "the input batch was written"
-    # device == host, on every output byte
+    _check_host(r, data, offs, lens, results, n_netifs, region, index_cap, tx, jumbo)
+    return r, want
+
+
+def _check_host(r, data, offs, lens, results, n_netifs, region, index_cap, tx=False, jumbo=False):
+    """device == host, on every output byte"""
+    from halo_amd import loopback as L
+
     h = L.gather_host(data, offs, lens, results, n_netifs, region, index_cap, tx=tx, jumbo=jumbo,
                       out=np.full(n_netifs * region + 64, FILL, np.uint8), skipped=np.full(1, 7, np.uint32))
     assert np.array_equal(r.out.cpu().numpy(), h.out) and np.array_equal(r.ports, h.ports) and r.n_skipped == h.n_skipped
     for p in range(n_netifs):
         assert np.array_equal(r.pkt_off_dw(p), h.pkt_off_dw(p)) and np.array_equal(r.pkt_len(p), h.pkt_len(p))
         assert np.array_equal(r.index(p), h.index(p))
-    return r, want
+    return h
 
 
 @pytest.mark.parametrize("tx", [False, True], ids=["forward", "tx"])
@@ -231,6 +237,45 @@ def test_past_the_scan_edges(dev, edge, r):
     assert np.array_equal(r_.index_raw.cpu().numpy().view(np.uint32), w_idx)
     assert r_.n_skipped == 0
     assert torch.equal(d, torch.from_numpy(data).to(dev)), "the input batch was written"
+
+
+@pytest.mark.parametrize("tx", [False, True], ids=["forward", "tx"])
+def test_past_one_grid(dev, tx):
+    """The first n past one grid of the count and scatter kernels, plus 299: the workgroups of the
+    first tiles take a second tile. Frames of 64 bytes repeating 1,000 templates (in tx mode
+    totalLen 20..51, so that lengths vary and one template in 32 is skipped), one frame in 64
+    selected by an irregular pattern, to two NetIfs; among them the batch's last frames, so that
+    both NetIfs have packets in a second-trip tile, and the region cuts both there or shortly
+    before. Every output byte against the host loop (tests/test_lo_host.py holds it to the model)."""
+    from halo_amd import loopback as L
+
+    n = C.past("lo_grid", 299)
+    first_trip = C.BOUNDARIES["lo_grid"]["first_past"] - 1
+    rng = np.random.default_rng(41)
+    templates = rng.integers(0, 256, (1000, 64), dtype=np.uint8)
+    templates[:, 16], templates[:, 17] = 0, 20 + np.arange(1000) % 32
+    data = np.ascontiguousarray(np.tile(templates.reshape(-1), n // 1000 + 1)[:n * 64])
+    offs, lens = (np.arange(n, dtype=np.int64) * 16).astype(np.uint32), np.full(n, 64, np.uint16)
+    i = np.arange(n, dtype=np.uint64)
+    h = i * np.uint64(2654435761) >> np.uint64(13)
+    chosen = h % np.uint64(64) == 0
+    chosen[first_trip::7] = chosen[n - 1] = True  # the second trip's tiles, their last frame included
+    assert chosen[n - 1] and 60 < n / int(chosen.sum()) < 68
+    results = np.zeros(n, C.ARP_RESULT_DTYPE)
+    results["verdict"] = np.where(chosen, AM.LOOPBACK, AM.HIT)
+    results["out_netif"] = (h >> np.uint64(7)) % np.uint64(2)
+    results["out_netif"][first_trip:] = np.arange(n - first_trip) % 2
+    free = L.gather_host(data, offs, lens, results, 2, 1 << 20, 0, tx=tx)
+    assert np.array_equal(free.ports["frames_written"], free.ports["frames"])
+    late = results["out_netif"][first_trip:][chosen[first_trip:]]
+    assert set(late.tolist()) == {0, 1} and (free.n_skipped > 0) == tx
+    region = (int(free.ports["bytes"].min()) - 16) & ~15
+    index_cap = int(free.ports["frames"].max()) + 3
+    d, o, ln, res = _up(dev, data, offs, lens, results)
+    r = _gather(dev, d, o, ln, res, 2, region, index_cap, tx)
+    host = _check_host(r, data, offs, lens, results, 2, region, index_cap, tx)
+    assert all(0 < int(p["frames_written"]) < int(p["frames"]) for p in host.ports)
+    assert np.array_equal(d.cpu().numpy(), data), "the input batch was written"
 
 
 def test_gathered_batch_parses_as_l3_packets(dev):

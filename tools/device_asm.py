@@ -13,7 +13,8 @@ Clang derives __hip_cuid_<16 hex> / __hip_gpubin_handle_<16 hex> from the file's
 name, so that a kernel that moved to another file keeps its line: the hash of its body, the hash of its
 kernel descriptor (.amdhsa_*: registers, LDS, scratch; "-" for a function that is no kernel), the build
 (lib / bench) and the symbol. ';' comments are dropped, and the function's ordinal in its module is masked
-where labels carry it (.LBB<n>_<k>, .LJTI<n>_<k>): it changes with the kernels around it.
+where labels carry it (.LBB<n>_<k>, .LJTI<n>_<k>): it changes with the kernels around it. The function's own
+symbol is masked in its body and in its descriptor, so that a renamed kernel keeps its hashes.
 """
 import hashlib
 import os
@@ -61,8 +62,8 @@ def kernels(root, src, flags):
         desc = b"-"
         if b"\t.amdhsa_kernel " + sym in lines:
             d = lines[lines.index(b"\t.amdhsa_kernel " + sym):]
-            desc = hashlib.sha256(b"\n".join(d[:d.index(b"\t.end_amdhsa_kernel") + 1])).hexdigest().encode()
-        found[sym.decode()] = (hashlib.sha256(b"\n".join(body)).hexdigest(), desc.decode())
+            desc = hashlib.sha256(b"\n".join(d[:d.index(b"\t.end_amdhsa_kernel") + 1]).replace(sym, b"SELF")).hexdigest().encode()
+        found[sym.decode()] = (hashlib.sha256(b"\n".join(body).replace(sym, b"SELF")).hexdigest(), desc.decode())
     return found
 
 
