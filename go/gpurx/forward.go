@@ -22,7 +22,8 @@ func RouteBatch(t *C.halo_route_table_t, dRecords unsafe.Pointer, n int, dIds un
 // buckets (hashmap/hashmap.go:64), for a caller that keeps NatWanFlowTable in Go and probes its
 // buckets without hashing. A NATing interface whose table lives behind halo_nat_table_t does not
 // need it: NatLookupWan / NatLookupLan / NatLookupQuote below hash, probe and fill the ops on the
-// device, and only new flows come back to the host (halo_nat_resolve_misses).
+// device, and only new flows come back to the host (halo_nat_resolve_misses, or one item per new
+// key through NatCollectMisses / NatResolveItems / NatApplyAnswers).
 func NatKeys(dRecords unsafe.Pointer, n int, natType int, dHash, dBucket unsafe.Pointer, nb uint32) error {
 	return halo(C.halo_flow_hash_device((*C.halo_rx_result_t)(dRecords), C.uint32_t(n), C.HALO_FLOW_NAT_WAN,
 		C.uint32_t(natType), (*C.uint64_t)(dHash), C.uint32_t(nb), (*C.uint32_t)(dBucket), nil))
@@ -44,12 +45,66 @@ func NatLookupWan(t *C.halo_nat_table_t, dRecords unsafe.Pointer, n int, now uin
 // NatLookupLan is the outbound half (engine/ipv4_engine.go:203-225) on the out-interface's table:
 // CheckNatPortMapping(LanToWan) else NatGetFlowByHash; a hit ORs HALO_TX_NAT_SRC and writes src_ip /
 // src_port. A miss is a new flow: copy the MISS records back and run halo_nat_resolve_misses, which
-// calls NatAddFlow in packet order.
+// calls NatAddFlow in packet order, or take the miss path below, which leaves the batch in HBM.
 func NatLookupLan(t *C.halo_nat_table_t, dRecords unsafe.Pointer, n int, now uint32, dSkip, dOps, dVerdict, dRef,
 	dMissCount unsafe.Pointer) error {
 	return halo(C.halo_nat_lookup_lan_device(t, (*C.halo_rx_result_t)(dRecords), C.uint32_t(n), C.uint32_t(now),
 		(*C.uint8_t)(dSkip), (*C.halo_tx_op_t)(dOps), (*C.uint8_t)(dVerdict), (*C.uint32_t)(dRef),
 		(*C.uint32_t)(dMissCount), nil))
+}
+
+// The miss path: what halo_nat_resolve_misses does for a batch, with records, verdicts and ops left
+// in HBM. NatCollectMisses lists the records NatLookupLan / NatLookupWan left as HALO_NAT_V_MISS,
+// once per key and in packet order; the caller copies *dCount and that many items to the host,
+// NatResolveItems runs CheckNatPortMapping / the flow lookup / NatAddFlow on each, the caller copies
+// the answers back, and NatApplyAnswers writes them into dOps / dVerdict / dRef of every record of a
+// listed key. A new flow's first packets then leave with their SNAT in the batch that created it.
+
+// NatMissWorkspace is the device scratch NatCollectMisses needs for n records (scratchLog2 0:
+// automatic).
+func NatMissWorkspace(n int, scratchLog2 uint32) uint64 {
+	return uint64(C.halo_nat_miss_workspace(C.uint32_t(n), C.uint32_t(scratchLog2)))
+}
+
+// NatCollectMisses: dir is HALO_FLOW_NAT_LAN or HALO_FLOW_NAT_WAN; dSelect (optional, one byte per
+// record) narrows the MISS records, e.g. to the packets whose TTL survives; dItems receives up to
+// itemCap halo_nat_miss_item_t, *dCount the number listed, dPos[i] the list position of record i's
+// key (HALO_NAT_NO_FLOW where not selected).
+func NatCollectMisses(t *C.halo_nat_table_t, dir uint32, dRecords, dVerdict, dSelect unsafe.Pointer, n int,
+	scratchLog2 uint32, dItems unsafe.Pointer, itemCap int, dCount, dPos, dWs unsafe.Pointer, wsBytes uint64) error {
+	return halo(C.halo_nat_collect_misses_device(t, C.uint32_t(dir), (*C.halo_rx_result_t)(dRecords),
+		(*C.uint8_t)(dVerdict), (*C.uint8_t)(dSelect), C.uint32_t(n), C.uint32_t(scratchLog2),
+		(*C.halo_nat_miss_item_t)(dItems), C.uint32_t(itemCap), (*C.uint32_t)(dCount), (*C.uint32_t)(dPos), dWs,
+		C.uint64_t(wsBytes), nil))
+}
+
+// NatCollectMissesCompact is NatCollectMisses over halo_rx_record16_t records.
+func NatCollectMissesCompact(t *C.halo_nat_table_t, dir uint32, dRecords, dVerdict, dSelect unsafe.Pointer, n int,
+	scratchLog2 uint32, dItems unsafe.Pointer, itemCap int, dCount, dPos, dWs unsafe.Pointer, wsBytes uint64) error {
+	return halo(C.halo_nat_collect_misses_compact_device(t, C.uint32_t(dir), (*C.halo_rx_record16_t)(dRecords),
+		(*C.uint8_t)(dVerdict), (*C.uint8_t)(dSelect), C.uint32_t(n), C.uint32_t(scratchLog2),
+		(*C.halo_nat_miss_item_t)(dItems), C.uint32_t(itemCap), (*C.uint32_t)(dCount), (*C.uint32_t)(dPos), dWs,
+		C.uint64_t(wsBytes), nil))
+}
+
+// NatResolveItems answers k listed items (host memory) in order on the authoritative table and
+// returns the number of flows NatAddFlow created.
+func NatResolveItems(t *C.halo_nat_table_t, dir uint32, items unsafe.Pointer, k int, now uint32,
+	answers unsafe.Pointer) (int, error) {
+	var added C.uint32_t
+	err := halo(C.halo_nat_resolve_items(t, C.uint32_t(dir), (*C.halo_nat_miss_item_t)(items), C.uint32_t(k),
+		C.uint32_t(now), (*C.halo_nat_answer_t)(answers), &added))
+	return int(added), err
+}
+
+// NatApplyAnswers writes the k answers (device memory, 16-byte aligned) into the ops, verdicts and
+// refs of the records whose dPos is below k; dCounts (optional, HALO_NAT_V_DROP+1 u32) is incremented
+// per verdict. A record the host answered HALO_NAT_V_DROP must not be transmitted.
+func NatApplyAnswers(dir uint32, dPos unsafe.Pointer, n int, dAnswers unsafe.Pointer, k int, dOps, dVerdict, dRef,
+	dCounts unsafe.Pointer) error {
+	return halo(C.halo_nat_apply_answers_device(C.uint32_t(dir), (*C.uint32_t)(dPos), C.uint32_t(n),
+		(*C.halo_nat_answer_t)(dAnswers), C.uint32_t(k), (*C.halo_tx_op_t)(dOps), (*C.uint8_t)(dVerdict),
+		(*C.uint32_t)(dRef), (*C.uint32_t)(dCounts), nil))
 }
 
 // NatLookupQuote is IcmpTtlDeepNat's NatGetFlowByWan (engine/icmp_engine.go:75-82) between DeepNat's

@@ -117,6 +117,11 @@ NAT_LAYOUT_DTYPE = np.dtype([("slots", "<u4"), ("port_mappings", "<u4"), ("entri
 NAT_NO_FLOW = 0xFFFFFFFF
 NAT_MAX_PORT_MAPPINGS = 256
 NAT_V_NONE, NAT_V_SKIP, NAT_V_MISS, NAT_V_FLOW, NAT_V_MAPPING, NAT_V_DROP = range(6)
+# the miss path: halo_nat_miss_item_t (20 bytes) and halo_nat_answer_t (16 bytes)
+NAT_MISS_ITEM_DTYPE = np.dtype([("index", "<u4"), ("src_ip", "<u4"), ("dst_ip", "<u4"), ("sport", "<u2"), ("dport", "<u2"),
+                                ("proto", "u1"), ("pad", "u1", (3,))])
+NAT_ANSWER_DTYPE = np.dtype([("ip", "<u4"), ("ref", "<u4"), ("port", "<u2"), ("verdict", "u1"), ("pad", "u1", (5,))])
+assert NAT_MISS_ITEM_DTYPE.itemsize == 20 and NAT_ANSWER_DTYPE.itemsize == 16
 # the L2 switch: halo_sw_result_t (4 bytes), halo_switch_entry_t (12 bytes), halo_switch_layout_stats_t, HALO_SW_V_*
 SW_RESULT_DTYPE = np.dtype([("verdict", "u1"), ("out_port", "u1"), ("tx_len", "<u2")])
 SW_ENTRY_DTYPE = np.dtype([("mac", "u1", (6,)), ("port", "u1"), ("pad", "u1"), ("create_time", "<u4")])
@@ -527,6 +532,16 @@ _PROTOS = {
         ctypes.c_void_p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, _u8p, ctypes.c_void_p])
        for d in ("wan", "lan") for c in ("", "_compact")},
     "halo_nat_lookup_quote_device": (ctypes.c_int, [ctypes.c_void_p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_void_p]),
+    "halo_nat_miss_workspace": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32]),
+    **{f"halo_nat_collect_misses{c}_device": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, ctypes.c_uint32,
+        _u8p, _u8p, _u8p, ctypes.c_uint64, ctypes.c_void_p]) for c in ("", "_compact")},
+    "halo_nat_collect_misses_host": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, _u8p, _u8p, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, _u8p]),
+    "halo_nat_resolve_items": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_uint32, _u8p, ctypes.c_uint32, ctypes.c_uint32, _u8p, ctypes.POINTER(ctypes.c_uint32)]),
+    "halo_nat_apply_answers_device": (ctypes.c_int, [
+        ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, ctypes.c_uint32, _u8p, _u8p, _u8p, _u8p, ctypes.c_void_p]),
     "halo_switch_create": (ctypes.c_int, [ctypes.POINTER(SwitchConfig), ctypes.POINTER(ctypes.c_void_p)]),
     "halo_switch_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "halo_switch_flood_mask": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]),

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "halo_amd", "csrc")
 OUT = os.path.join(ROOT, "halo_amd", "lib", "libhalo_rx.so")
 SOURCES = ["rx_lane.hip", "rx_group.hip", "rx_stream.hip", "rx_parse.hip", "rx_hist.hip", "tx_fixup.hip", "tx_build.hip", "deep_nat.hip", "flow_hash.hip", "route_lpm.hip", "synth.hip", "host_path.hip",
-           "ring_rx.hip", "resident.hip", "host_logic.cc", "nat_lookup.hip", "nat_table.cc", "switch_fwd.hip", "switch_table.cc",
+           "ring_rx.hip", "resident.hip", "host_logic.cc", "nat_lookup.hip", "nat_miss.hip", "nat_table.cc", "switch_fwd.hip", "switch_table.cc",
            "arp_fwd.hip", "arp_table.cc", "tx_egress.hip", "tx_egress_host.cc", "tx_respond.hip", "tx_respond_host.cc",
            "pmflow_fwd.hip", "pmflow_table.cc", "tx_ring.hip", "tx_ring_host.cc", "rx_deliver.hip", "rx_deliver_host.cc",
            "rx_kcp.hip", "rx_kcp_host.cc", "tx_kcp.hip", "tx_kcp_host.cc", "rx_dhcp.hip", "rx_dhcp_host.cc", "tx_dhcp.hip",

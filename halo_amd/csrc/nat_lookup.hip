@@ -253,11 +253,27 @@ int ops_quote(const halo_nat_table* t, const halo_rx_result_t* d_quote_records, 
     return hipGetLastError() == hipSuccess ? HALO_OK : HALO_E_HIP;
 }
 
+// The miss path's collect (nat_miss.hip) reads no table, only its NAT type; it is refused before
+// the first sync as the lookups are.
+template <bool COMPACT>
+int ops_collect(const halo_nat_table* t, uint32_t dir, const void* d_records, const uint8_t* d_verdict,
+                const uint8_t* d_select, uint32_t n, uint32_t slots, halo_nat_miss_item_t* d_items, uint32_t cap,
+                uint32_t* d_count, uint32_t* d_pos, void* d_workspace, halo_stream_t stream) {
+    NatDevice* d = dev_of<NatDevice>(t);
+    if (!d) return HALO_E_INVAL;  // never synced
+    {
+        std::shared_lock<std::shared_mutex> lk(d->view_mu);
+        if (!d->published()) return HALO_E_INVAL;
+    }
+    return nat::miss_collect(dir, t->cfg.nat_type, COMPACT, d_records, d_verdict, d_select, n, slots, d_items, cap, d_count,
+                             d_pos, d_workspace, stream);
+}
+
 // (the lookups in DeviceOps' order: the kernels are emitted in the order they are first named)
 const nat::DeviceOps kDeviceOps = {
     ops_sync, fold_entry<NatDevice, halo_nat_table>, publish_entry<NatDevice, halo_nat_table>, destroy<NatDevice, halo_nat_table>,
     lookup<HALO_FLOW_NAT_WAN, false>, lookup<HALO_FLOW_NAT_LAN, false>, lookup<HALO_FLOW_NAT_WAN, true>, lookup<HALO_FLOW_NAT_LAN, true>,
-    ops_quote};
+    ops_quote, ops_collect<false>, ops_collect<true>, nat::miss_apply};
 
 }  // namespace
 

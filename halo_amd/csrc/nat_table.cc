@@ -206,6 +206,50 @@ extern "C" HALO_API int halo_nat_get_flow_wan(const halo_nat_table_t* t, uint32_
     return HALO_OK;
 }
 
+namespace {
+
+// One record of the miss slow path, t.mu held: CheckNatPortMapping, then the host flow lookup,
+// then (LAN) NatAddFlow; nil is DROP (:214-217), a WAN miss stays MISS (:120-124), a hit stamps
+// the flow. The one copy halo_nat_resolve_misses and halo_nat_resolve_items share.
+halo_nat_answer_t resolve_one(halo_nat_table& t, bool wan, uint32_t proto, uint32_t src_ip, uint32_t dst_ip, uint32_t sport,
+                              uint32_t dport, uint32_t now, uint32_t* added) {
+    halo_nat_answer_t a{};
+    a.ref = HALO_NAT_NO_FLOW;
+    a.verdict = HALO_NAT_V_MISS;
+    const int m = wan ? check_mapping(t, HALO_FLOW_NAT_WAN, 0, dport, proto) : check_mapping(t, HALO_FLOW_NAT_LAN, src_ip, sport, proto);
+    if (m >= 0) {
+        const PortMapping& e = t.maps[(size_t)m];
+        a.ip = wan ? e.lan_ip : t.cfg.wan_ip;
+        a.port = wan ? e.lan_port : e.wan_port;
+        a.ref = (uint32_t)m;
+        a.verdict = HALO_NAT_V_MAPPING;
+        return a;
+    }
+    Flow* f;
+    if (wan) {
+        f = find(t.wan, norm_key(t, src_ip, sport, dst_ip, dport, proto));
+        if (!f) return a;  // stays MISS: local delivery (:120-124)
+    } else {
+        f = find(t.lan, norm_key(t, dst_ip, dport, src_ip, sport, proto));
+        if (!f) {
+            f = add_flow(t, src_ip, dst_ip, sport, dport, proto, now);
+            if (!f) {
+                a.verdict = HALO_NAT_V_DROP;  // :214-217
+                return a;
+            }
+            ++*added;
+        }
+    }
+    f->f.last_alive = now;
+    a.ip = wan ? f->f.lan_ip : f->f.wan_ip;
+    a.port = wan ? f->f.lan_port : f->f.wan_port;
+    a.ref = f->f.id;
+    a.verdict = HALO_NAT_V_FLOW;
+    return a;
+}
+
+}  // namespace
+
 extern "C" HALO_API int halo_nat_resolve_misses(halo_nat_table_t* t, uint32_t dir, const halo_rx_result_t* records,
                                                 const uint8_t* verdicts, uint32_t n, uint32_t now, halo_tx_op_t* ops,
                                                 uint8_t* verdicts_out, uint32_t* n_added) {
@@ -221,51 +265,119 @@ extern "C" HALO_API int halo_nat_resolve_misses(halo_nat_table_t* t, uint32_t di
         verdicts_out[i] = v;
         if (v != HALO_NAT_V_MISS) continue;
         const halo_rx_result_t& r = records[i];
+        const halo_nat_answer_t a = resolve_one(*t, wan, r.ip_proto, r.src_ip, r.dst_ip, r.sport, r.dport, now, &added);
+        verdicts_out[i] = a.verdict;
+        if (a.verdict != HALO_NAT_V_FLOW && a.verdict != HALO_NAT_V_MAPPING) continue;
         halo_tx_op_t& op = ops[i];
-        const int m = wan ? check_mapping(*t, dir, 0, r.dport, r.ip_proto) : check_mapping(*t, dir, r.src_ip, r.sport, r.ip_proto);
-        if (m >= 0) {
-            const PortMapping& e = t->maps[(size_t)m];
-            if (wan) {
-                op.steps |= HALO_TX_NAT_DST;
-                op.dst_ip = e.lan_ip;
-                op.dst_port = e.lan_port;
-            } else {
-                op.steps |= HALO_TX_NAT_SRC;
-                op.src_ip = t->cfg.wan_ip;
-                op.src_port = e.wan_port;
-            }
-            verdicts_out[i] = HALO_NAT_V_MAPPING;
-            continue;
-        }
-        Flow* f;
-        if (wan) {
-            f = find(t->wan, norm_key(*t, r.src_ip, r.sport, r.dst_ip, r.dport, r.ip_proto));
-            if (!f) continue;  // stays MISS: local delivery (:120-124)
-        } else {
-            f = find(t->lan, norm_key(*t, r.dst_ip, r.dport, r.src_ip, r.sport, r.ip_proto));
-            if (!f) {
-                f = add_flow(*t, r.src_ip, r.dst_ip, r.sport, r.dport, r.ip_proto, now);
-                if (!f) {
-                    verdicts_out[i] = HALO_NAT_V_DROP;  // :214-217
-                    continue;
-                }
-                ++added;
-            }
-        }
-        f->f.last_alive = now;
         if (wan) {
             op.steps |= HALO_TX_NAT_DST;
-            op.dst_ip = f->f.lan_ip;
-            op.dst_port = f->f.lan_port;
+            op.dst_ip = a.ip;
+            op.dst_port = a.port;
         } else {
             op.steps |= HALO_TX_NAT_SRC;
-            op.src_ip = f->f.wan_ip;
-            op.src_port = f->f.wan_port;
+            op.src_ip = a.ip;
+            op.src_port = a.port;
         }
-        verdicts_out[i] = HALO_NAT_V_FLOW;
     }
     if (n_added) *n_added = added;
     return HALO_OK;
+}
+
+extern "C" HALO_API int halo_nat_resolve_items(halo_nat_table_t* t, uint32_t dir, const halo_nat_miss_item_t* items,
+                                               uint32_t k, uint32_t now, halo_nat_answer_t* answers, uint32_t* n_added) {
+    if (!t || (dir != HALO_FLOW_NAT_LAN && dir != HALO_FLOW_NAT_WAN)) return HALO_E_INVAL;
+    if (n_added) *n_added = 0;
+    if (k == 0) return HALO_OK;
+    if (!items || !answers) return HALO_E_INVAL;
+    uint32_t added = 0;
+    std::lock_guard<std::mutex> g(t->mu);
+    for (uint32_t j = 0; j < k; ++j) {  // list order = ascending record index
+        const halo_nat_miss_item_t& it = items[j];
+        answers[j] = resolve_one(*t, dir == HALO_FLOW_NAT_WAN, it.proto, it.src_ip, it.dst_ip, it.sport, it.dport, now, &added);
+    }
+    if (n_added) *n_added = added;
+    return HALO_OK;
+}
+
+// A LAN record no other record may answer for, and that answers for no other (include/halo_rx.h,
+// "the miss path"): NatAddFlow refuses its raw remote port 0, yet its normalised key may be shared.
+static bool miss_listed_alone(uint32_t dir, uint32_t sport, uint32_t dport) {
+    return dir == HALO_FLOW_NAT_LAN && dport == 0 && sport != 0;
+}
+
+extern "C" HALO_API int halo_nat_collect_misses_host(const halo_nat_table_t* t, uint32_t dir,
+                                                     const halo_rx_result_t* records, const uint8_t* verdict,
+                                                     const uint8_t* select, uint32_t n, halo_nat_miss_item_t* items,
+                                                     uint32_t cap, uint32_t* count, uint32_t* pos) {
+    if (!t || (dir != HALO_FLOW_NAT_LAN && dir != HALO_FLOW_NAT_WAN) || !count || (cap && !items)) return HALO_E_INVAL;
+    if (n && (!records || !verdict || !pos)) return HALO_E_INVAL;
+    std::unordered_map<Key, uint32_t, KeyHash, KeyEq> first;  // normalised key -> list position
+    uint32_t k = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        pos[i] = HALO_NAT_NO_FLOW;
+        if (verdict[i] != HALO_NAT_V_MISS || (select && !select[i])) continue;
+        const halo_rx_result_t& r = records[i];
+        if (!miss_listed_alone(dir, r.sport, r.dport)) {
+            const auto ins =
+                first.emplace(halo::flowkey::nat_key(r.ip_proto, r.src_ip, r.dst_ip, r.sport, r.dport, dir, t->cfg.nat_type), k);
+            if (!ins.second) {
+                pos[i] = ins.first->second;
+                continue;
+            }
+        }
+        if (k < cap) {
+            halo_nat_miss_item_t it{};
+            it.index = i, it.src_ip = r.src_ip, it.dst_ip = r.dst_ip, it.sport = r.sport, it.dport = r.dport, it.proto = r.ip_proto;
+            items[k] = it;
+        }
+        pos[i] = k++;
+    }
+    *count = k;
+    return HALO_OK;
+}
+
+extern "C" HALO_API uint64_t halo_nat_miss_workspace(uint32_t n, uint32_t scratch_log2) {
+    const uint64_t slots = miss_slots(n, scratch_log2);
+    const uint64_t tiles = miss_tiles(n);
+    return slots ? 4 * (slots + (tiles ? tiles : 1) + n) : 0;
+}
+
+// halo_nat_collect_misses_device and halo_nat_collect_misses_compact_device: the argument checks,
+// then DeviceOps::collect / collect_compact.
+#define HALO_NAT_COLLECT(NAME, RECORD, OP)                                                                              \
+    extern "C" HALO_API int NAME(const halo_nat_table_t* t, uint32_t dir, const RECORD* d_records,                      \
+                                 const uint8_t* d_verdict, const uint8_t* d_select, uint32_t n, uint32_t scratch_log2,  \
+                                 halo_nat_miss_item_t* d_items, uint32_t cap, uint32_t* d_count, uint32_t* d_pos,       \
+                                 void* d_workspace, uint64_t workspace_bytes, halo_stream_t stream) {                   \
+        if (!t || (dir != HALO_FLOW_NAT_LAN && dir != HALO_FLOW_NAT_WAN) || !d_count || (cap && !d_items))              \
+            return HALO_E_INVAL;                                                                                        \
+        if (n && (!d_records || !d_verdict || !d_pos || !d_workspace)) return HALO_E_INVAL;                             \
+        if (reinterpret_cast<uintptr_t>(d_records) & 15u) return HALO_E_INVAL;                                          \
+        if ((reinterpret_cast<uintptr_t>(d_items) | reinterpret_cast<uintptr_t>(d_count) |                              \
+             reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_workspace)) & 3u)                       \
+            return HALO_E_INVAL;                                                                                        \
+        const uint32_t slots = miss_slots(n, scratch_log2);                                                             \
+        if (slots <= n) return HALO_E_RANGE;                                                                            \
+        if (n && workspace_bytes < halo_nat_miss_workspace(n, scratch_log2)) return HALO_E_INVAL;                       \
+        if (!device_ops) return HALO_E_NODEV;                                                                           \
+        return device_ops()->OP(t, dir, d_records, d_verdict, d_select, n, slots, d_items, cap, d_count, d_pos,         \
+                                d_workspace, stream);                                                                   \
+    }
+HALO_NAT_COLLECT(halo_nat_collect_misses_device, halo_rx_result_t, collect)
+HALO_NAT_COLLECT(halo_nat_collect_misses_compact_device, halo_rx_record16_t, collect_compact)
+#undef HALO_NAT_COLLECT
+
+extern "C" HALO_API int halo_nat_apply_answers_device(uint32_t dir, const uint32_t* d_pos, uint32_t n,
+                                                      const halo_nat_answer_t* d_answers, uint32_t k, halo_tx_op_t* d_ops,
+                                                      uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_counts,
+                                                      halo_stream_t stream) {
+    if (dir != HALO_FLOW_NAT_LAN && dir != HALO_FLOW_NAT_WAN) return HALO_E_INVAL;
+    if (n && (!d_pos || !d_ops || !d_verdict || !d_ref || (k && !d_answers))) return HALO_E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(d_answers) | reinterpret_cast<uintptr_t>(d_ops)) & 15u) return HALO_E_INVAL;
+    if ((reinterpret_cast<uintptr_t>(d_pos) | reinterpret_cast<uintptr_t>(d_ref) | reinterpret_cast<uintptr_t>(d_counts)) & 3u)
+        return HALO_E_INVAL;
+    if (!device_ops) return HALO_E_NODEV;
+    return device_ops()->apply(dir, d_pos, n, d_answers, k, d_ops, d_verdict, d_ref, d_counts, stream);
 }
 
 extern "C" HALO_API int halo_nat_expire(halo_nat_table_t* t, uint32_t now, uint32_t* n_removed) {

@@ -89,7 +89,35 @@ struct DeviceOps {
     Lookup lookup_wan, lookup_lan, lookup_wan_compact, lookup_lan_compact;  // compact: d_records are halo_rx_record16_t
     int (*quote)(const halo_nat_table* t, const halo_rx_result_t* d_quote_records, uint32_t n, halo_tx_deep_nat_t* d_nat,
                  halo_stream_t stream);
+    // the miss path (nat_miss.hip); arguments checked by nat_table.cc, `slots` from miss_slots
+    using Collect = int (*)(const halo_nat_table* t, uint32_t dir, const void* d_records, const uint8_t* d_verdict,
+                            const uint8_t* d_select, uint32_t n, uint32_t slots, halo_nat_miss_item_t* d_items, uint32_t cap,
+                            uint32_t* d_count, uint32_t* d_pos, void* d_workspace, halo_stream_t stream);
+    Collect collect, collect_compact;
+    int (*apply)(uint32_t dir, const uint32_t* d_pos, uint32_t n, const halo_nat_answer_t* d_answers, uint32_t k,
+                 halo_tx_op_t* d_ops, uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_counts, halo_stream_t stream);
 };
+// The miss path's kernels (nat_miss.hip); nat_lookup.hip puts them behind DeviceOps once it has
+// seen a published device copy.
+int miss_collect(uint32_t dir, uint32_t nat_type, bool compact, const void* d_records, const uint8_t* d_verdict,
+                 const uint8_t* d_select, uint32_t n, uint32_t slots, halo_nat_miss_item_t* d_items, uint32_t cap,
+                 uint32_t* d_count, uint32_t* d_pos, void* d_workspace, halo_stream_t stream);
+int miss_apply(uint32_t dir, const uint32_t* d_pos, uint32_t n, const halo_nat_answer_t* d_answers, uint32_t k,
+               halo_tx_op_t* d_ops, uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_counts, halo_stream_t stream);
+
+// The collect's geometry, shared by the workspace size and the launch: 256-record tiles; the
+// scratch table's slot count (0: out of range); and the workspace as u32 owner[slots], then
+// tiles[n_tiles], then link[n].
+constexpr uint32_t kMissTile = 256;
+inline uint32_t miss_slots(uint32_t n, uint32_t scratch_log2) {
+    if (scratch_log2 > 31) return 0;
+    if (scratch_log2) return 1u << scratch_log2;
+    if (n > (1u << 30)) return 0;
+    uint32_t s = 16;
+    while (s < 2 * n) s <<= 1;
+    return s;
+}
+inline uint32_t miss_tiles(uint32_t n) { return n / kMissTile + (n % kMissTile ? 1u : 0u); }
 // Defined by nat_lookup.hip; absent (null) in a host-only build, where the device calls are HALO_E_NODEV.
 const DeviceOps* device_ops() __attribute__((weak));
 

@@ -4,7 +4,9 @@
 (engine/ipv4_engine.go:524-759) run on the host table through the C ABI; ``sync()`` compiles it
 into the device's open-addressing tables; ``lookup_wan / lookup_lan / lookup_quote`` run the
 forward path's lookups over device-resident parsed records and fill the ``halo_tx_op_t`` array of
-``halo_tx_fixup_batch_device``; ``resolve_misses`` is the host slow path for new flows.
+``halo_tx_fixup_batch_device``. New flows take one of two slow paths: ``resolve_misses`` over host
+copies of the whole batch, or ``resolve_misses_device`` (``collect_misses`` -> ``resolve_items`` ->
+``apply_answers``), which leaves the batch in HBM and brings one item per new key to the host.
 """
 from __future__ import annotations
 
@@ -13,8 +15,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import (FLOW_NAT_LAN, FLOW_NAT_WAN, NAT_FLOW_DTYPE, NAT_LAYOUT_DTYPE, NAT_NO_FLOW,  # noqa: F401
-                   NAT_V_DROP, NAT_V_FLOW, NAT_V_MAPPING, NAT_V_MISS, NAT_V_NONE, NAT_V_SKIP, TX_OP_DTYPE)
+from ._lib import (FLOW_NAT_LAN, FLOW_NAT_WAN, NAT_ANSWER_DTYPE, NAT_FLOW_DTYPE, NAT_LAYOUT_DTYPE,  # noqa: F401
+                   NAT_MISS_ITEM_DTYPE, NAT_NO_FLOW, NAT_V_DROP, NAT_V_FLOW, NAT_V_MAPPING, NAT_V_MISS, NAT_V_NONE, NAT_V_SKIP, TX_OP_DTYPE)
 
 
 class NatTable:
@@ -94,7 +96,95 @@ class NatTable:
             _lib.ptr(out), ctypes.byref(added)))
         return out, int(added.value)
 
+    def collect_misses_host(self, direction: int, records: np.ndarray, verdict: np.ndarray, select=None, cap=None):
+        """halo_nat_collect_misses_host over host arrays: (items NAT_MISS_ITEM_DTYPE [min(count, cap)],
+        count, pos uint32 [n]) — the answer ``collect_misses`` must give."""
+        n = len(records)
+        assert records.dtype == _lib.RESULT_DTYPE and verdict.dtype == np.uint8 and len(verdict) == n
+        if select is not None:
+            select = np.ascontiguousarray(select, np.uint8)
+            assert len(select) == n
+        cap = n if cap is None else cap
+        items = np.zeros(max(cap, 1), NAT_MISS_ITEM_DTYPE)
+        pos = np.empty(max(n, 1), np.uint32)
+        count = np.zeros(1, np.uint32)
+        _lib.check("halo_nat_collect_misses_host", _lib.lib.halo_nat_collect_misses_host(
+            self._t, direction, _lib.ptr(records), _lib.ptr(verdict), _lib.ptr(select), n, _lib.ptr(items), cap,
+            _lib.ptr(count), _lib.ptr(pos)))
+        return items[:min(cap, int(count[0]))], int(count[0]), pos[:n]
+
+    def resolve_items(self, direction: int, items: np.ndarray, now: int):
+        """halo_nat_resolve_items over ``items`` in order: (answers NAT_ANSWER_DTYPE [k], n_added)."""
+        items = np.ascontiguousarray(items, NAT_MISS_ITEM_DTYPE)
+        k = int(items.shape[0])
+        answers = np.zeros(max(k, 1), NAT_ANSWER_DTYPE)
+        added = ctypes.c_uint32()
+        _lib.check("halo_nat_resolve_items", _lib.lib.halo_nat_resolve_items(
+            self._t, direction, _lib.ptr(items), k, now & 0xFFFFFFFF, _lib.ptr(answers), ctypes.byref(added)))
+        return answers[:k], int(added.value)
+
     # ---- device ------------------------------------------------------------------------------
+    @staticmethod
+    def _stream(stream):
+        import torch
+
+        return (stream if stream is not None else torch.cuda.current_stream()).cuda_stream
+
+    def collect_misses(self, direction: int, records, verdict, select=None, cap=None, scratch_log2: int = 0,
+                       workspace=None, stream=None):
+        """The records of a looked-up batch that are still MISS (and selected: ``select`` cuda uint8
+        [n], optional), once per key and in ascending index (cuda tensors: ``records`` uint8 [n, 32] or
+        compact [n, 16], ``verdict`` uint8 [n]): (items uint8 [cap, 20] = NAT_MISS_ITEM_DTYPE, count
+        int32 [1], pos int32 [n]). ``count`` is the number listed even when it exceeds ``cap`` (default
+        n); ``pos[i]`` is the list position of record i's key, -1 where not selected. ``workspace``
+        (int32, at least ``halo_nat_miss_workspace(n, scratch_log2)`` bytes) may be shared by calls on
+        one stream. Asynchronous."""
+        import torch
+
+        n = int(records.shape[0])
+        cap = n if cap is None else cap
+        dev = records.device
+        items = torch.zeros((max(cap, 1), 20), dtype=torch.uint8, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        pos = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+        if workspace is None:
+            need = int(_lib.lib.halo_nat_miss_workspace(n, scratch_log2))
+            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=dev)
+        name = f"halo_nat_collect_misses{'_compact' if records.shape[1] == 16 else ''}_device"
+        _lib.check(name, getattr(_lib.lib, name)(
+            self._t, direction, _lib.ptr(records), _lib.ptr(verdict), _lib.ptr(select), n, scratch_log2,
+            _lib.ptr(items), cap, _lib.ptr(count), _lib.ptr(pos), _lib.ptr(workspace),
+            workspace.numel() * workspace.element_size(), self._stream(stream)))
+        return items, count, pos
+
+    @classmethod
+    def apply_answers(cls, direction: int, pos, answers, ops, verdict, ref, counts=None, stream=None) -> None:
+        """halo_nat_apply_answers_device: the answers (cuda uint8 [k, 16] = NAT_ANSWER_DTYPE) of the
+        items ``collect_misses`` listed, written into ``ops`` / ``verdict`` / ``ref`` of every record
+        whose ``pos`` is below k. ``counts`` (cuda int32 [6], optional) is incremented per verdict."""
+        _lib.check("halo_nat_apply_answers_device", _lib.lib.halo_nat_apply_answers_device(
+            direction, _lib.ptr(pos), int(pos.shape[0]), _lib.ptr(answers), int(answers.shape[0]), _lib.ptr(ops),
+            _lib.ptr(verdict), _lib.ptr(ref), _lib.ptr(counts), cls._stream(stream)))
+
+    def resolve_misses_device(self, direction: int, records, ops, verdict, ref, now: int, select=None, stream=None):
+        """The miss path's round trip on device-resident arrays: collect, read ``count`` (one 4-byte
+        synchronising copy; 0 ends the call), download that many items, ``resolve_items`` on the host
+        table, upload the answers, apply. ``ops`` / ``verdict`` / ``ref`` end as ``resolve_misses`` over
+        host copies would leave them. Returns (n_listed, n_added)."""
+        import torch
+
+        items, count, pos = self.collect_misses(direction, records, verdict, select=select, stream=stream)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            k = int(count.cpu().numpy().view(np.uint32)[0])
+            if k == 0:
+                return 0, 0
+            host = items[:k].cpu().numpy().reshape(-1).view(NAT_MISS_ITEM_DTYPE)
+            answers, added = self.resolve_items(direction, host, now)
+            d_answers = torch.from_numpy(answers.view(np.uint8).reshape(k, 16)).to(records.device)
+        self.apply_answers(direction, pos, d_answers, ops, verdict, ref, stream=stream)
+        return k, added
+
     def sync(self):
         _lib.check("halo_nat_sync_device", _lib.lib.halo_nat_sync_device(self._t, self.device))
 

@@ -192,7 +192,7 @@ class ReturnFlows:
     ``pm_counts``, the out NetIf's ``nat_verdict`` / ``nat_ref`` / ``nat_miss`` (None without a NAT
     table), ``fixup_result`` and the encap's ``results`` / ``counts`` / ``miss_count`` — what
     ``egress_arp(data, offsets_dw, lens, results, ...)`` takes — and ``mark`` (``loopback.mark``'s, None
-    without ``loopback=True``)."""
+    without ``loopback=True``) and ``nat_new`` (``(n_listed, n_added)``, None without ``new_flows=True``)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -200,13 +200,21 @@ class ReturnFlows:
 
 def forward_return_flows(data, offsets_dw, lens, *, netif, in_netif: int, now: int, pmflow, routes, arp, nat=None,
                          records=None, steps: int = TX_TTL, check_sum_enable: bool = True, stream=None,
-                         loopback: bool = False) -> ReturnFlows:
+                         loopback: bool = False, new_flows: bool = False) -> ReturnFlows:
     """The forward chain for a batch a non-NAT NetIf received (cuda tensors as ``parse_frames_batch``),
     rewritten in place: parse (unless ``records`` is given) -> ``routes.FindRouteRecords`` ->
     ``pmflow.lookup`` -> ``nat.lookup_lan`` with the return-flow hits skipped (``nat``: the NAT table
     of the NetIf the routes point at, or None) -> fixup (TTL, then the SNAT the lookups chose) ->
     ``arp.encap_via`` for the frames whose TTL survived. No host round trip. A ``nat`` MISS (a new
     flow) keeps the caller's slow path, ``NatTable.resolve_misses``, as before.
+
+    ``new_flows=True`` (with a ``nat``) resolves those misses inside the chain instead:
+    ``nat.resolve_misses_device(LAN, ...)`` runs between ``nat.lookup_lan`` and the fixup — one item
+    per new key goes to the host table and comes back — so a new flow's first packets leave with their
+    SNAT in this batch. Only frames whose TTL byte is above 1 are selected (the reference returns at
+    :135-142, before any NatAddFlow, so a TTL-dead packet adds no flow), and the records the host
+    answered DROP are not passed to the encap (:214-217: nothing is transmitted). The result then
+    carries ``nat_new = (n_listed, n_added)``.
 
     ``loopback=True`` puts ``loopback.mark`` between ``pmflow.lookup`` and ``nat.lookup_lan``: a packet
     addressed to the out NetIf's own address is skipped by the NAT lookup as the return-flow hits are
@@ -234,12 +242,24 @@ def forward_return_flows(data, offsets_dw, lens, *, netif, in_netif: int, now: i
         skip = hit | lo_mark
     if nat is not None:
         ops, nat_verdict, nat_ref, nat_miss = nat.lookup_lan(records, now, ops=ops, skip=skip, stream=stream)
+    nat_new = None
+    if new_flows and nat is not None:
+        # the frame's TTL byte (Ethernet 14 + IPv4 8), for frames that reach it
+        at = (offsets_dw.to(torch.int64) & 0xFFFFFFFF) * 4 + 22
+        reach = (lens.to(torch.int32) & 0xFFFF) > 22
+        ttl = data[torch.where(reach, at, torch.zeros_like(at))]
+        select = (reach & (ttl > 1)).to(torch.uint8)
+        nat_new = nat.resolve_misses_device(_lib.FLOW_NAT_LAN, records, ops, nat_verdict, nat_ref, now, select=select,
+                                            stream=stream)
     fixup_result = torch.zeros(n, dtype=torch.uint8, device=data.device)
     protocol.tx_fixup_batch(data, offsets_dw, lens, ops.reshape(-1), check_sum_enable=check_sum_enable,
                             result=fixup_result, stream=stream)
     alive = fixup_result & protocol.TX_R_TTL_ALIVE
+    if nat_new is not None:
+        alive = alive * (nat_verdict != _lib.NAT_V_DROP)  # NatAddFlow returned nil: not transmitted
     results, counts, miss_count = arp.encap_via(data, offsets_dw, lens, route_ids, in_netif, via, select=alive,
                                                 stream=stream)
     return ReturnFlows(records=records, route_ids=route_ids, ops=ops, via=via, hit=hit, pm_counts=pm_counts,
                        nat_verdict=nat_verdict, nat_ref=nat_ref, nat_miss=nat_miss, fixup_result=fixup_result,
-                       alive=alive, results=results, counts=counts, miss_count=miss_count, mark=lo_mark)
+                       alive=alive, results=results, counts=counts, miss_count=miss_count, mark=lo_mark,
+                       nat_new=nat_new)

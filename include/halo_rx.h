@@ -695,8 +695,10 @@ HALO_API int halo_rx_parse_route_batch_device(const uint8_t* d_bytes, const uint
  * compiles both indexes and the port-mapping list into open-addressing tables in HBM, and the
  * lookups of Ipv4RouteForward's inbound (:111-130) and outbound (:203-225) halves and of
  * IcmpTtlDeepNat (engine/icmp_engine.go:55-86) run on the GPU over the parsed records, writing the
- * halo_tx_op_t array halo_tx_fixup_batch_device consumes. Only new flows (device MISS) take the
- * host slow path, halo_nat_resolve_misses. One table per NATing NetIf. All addresses are in
+ * halo_tx_op_t array halo_tx_fixup_batch_device consumes. Only new flows (device MISS) take a
+ * host slow path: halo_nat_resolve_misses over host copies of the whole batch, or the miss path
+ * below (halo_nat_collect_misses_device -> halo_nat_resolve_items -> halo_nat_apply_answers_device),
+ * which brings only one item per new key to the host. One table per NATing NetIf. All addresses are in
  * IpAddrToU form. The router-global NatPortMappingFlowTable (:160-186, :238-266) is its own
  * table ("port-mapping return flows" below). The ARP step that follows the rewrite is
  * halo_arp_encap_device ("ARP neighbour cache" below).
@@ -839,6 +841,96 @@ HALO_API int halo_nat_lookup_lan_compact_device(const halo_nat_table_t* t, const
  * neither). */
 HALO_API int halo_nat_lookup_quote_device(const halo_nat_table_t* t, const halo_rx_result_t* d_quote_records,
                                           uint32_t n, halo_tx_deep_nat_t* d_nat, halo_stream_t stream);
+
+/* The miss path: what halo_nat_resolve_misses does for a batch, with the records, verdicts and
+ * ops left in HBM. The host table stays the authority (ports are allocated there, in packet
+ * order); the device lists, once per key and in ascending record index, what the host must see
+ * (collect), the host answers each item (halo_nat_resolve_items), and the device writes the
+ * answers into the ops, verdicts and refs of every record of the key (apply). Over the same
+ * arrays the three calls leave the ops, the verdicts and the host table exactly as
+ * halo_nat_resolve_misses does.
+ *
+ * A record is SELECTED when d_verdict[i] == HALO_NAT_V_MISS and (d_select == NULL or
+ * d_select[i] != 0). Its key is the normalised key the lookup of `dir` uses (port 0 for ICMP's
+ * remote port, no remote half unless the table is symmetric). The REPRESENTATIVE of a selected
+ * record is the lowest-indexed selected record with the same key. Answering a key once is exact
+ * because a later record of the key meets what the first one left: a flow the first one added is
+ * a hit from then on; a port mapping or a WAN answer depends on nothing a record changes; and a
+ * DROP by port exhaustion repeats, since nothing frees a port inside a batch. ONE CLASS IS ORDER
+ * SENSITIVE and is never deduplicated: a LAN record with dport == 0 and sport != 0. NatAddFlow
+ * refuses a raw remotePort of 0 (engine/ipv4_engine.go:584-587), but the key is normalised first,
+ * so under full-cone NAT A(dport 0), B(dport 5), C(dport 0) of one LAN host and port share a key
+ * and give DROP, FLOW (added), FLOW (hit): copying A's DROP to B and C would be wrong. Each such
+ * record is listed on its own, is its own representative and nobody else's. A record with
+ * sport == 0 needs no such care: no flow with LAN port 0 can exist, so its answer (MAPPING or
+ * DROP) is a function of its key alone; a GRE or ESP flood lists one item. WAN has no adds: every
+ * WAN key is deduplicated. */
+typedef struct halo_nat_miss_item { /* 20 B, 4-byte aligned; the raw record fields, not normalised */
+    uint32_t index;                 /* the record's index in its batch (the first of its key) */
+    uint32_t src_ip, dst_ip;
+    uint16_t sport, dport;
+    uint8_t proto, pad[3];
+} halo_nat_miss_item_t;
+typedef struct halo_nat_answer { /* 16 B, 16-byte aligned on the device */
+    uint32_t ip;                 /* the translation a hit writes (dst_* for WAN, src_* for LAN) */
+    uint32_t ref;                /* flow id / mapping index / HALO_NAT_NO_FLOW */
+    uint16_t port;
+    uint8_t verdict;             /* HALO_NAT_V_FLOW / _MAPPING / _DROP / _MISS (WAN: stays MISS) */
+    uint8_t pad[5];
+} halo_nat_answer_t;
+/* Bytes of device scratch halo_nat_collect_misses_*device needs for n records (4-byte aligned): the
+ * in-batch table (u32 per slot), one u32 per 256-record tile and one u32 per record.
+ * scratch_log2 == 0: automatic, the power of two >= 2n (at least 16 slots); otherwise exactly
+ * 2^scratch_log2 slots (tests). 0 when the combination is out of range (scratch_log2 > 31, or
+ * n > 2^30 with automatic sizing). */
+HALO_API uint64_t halo_nat_miss_workspace(uint32_t n, uint32_t scratch_log2);
+/* Collect: d_items receives the representatives, densely, in ascending index; *d_count is SET to
+ * their number, also when it exceeds `cap` (only the first `cap` items are written); d_pos[i] =
+ * the list position of record i's representative, for every i < n (also a position >= cap), and
+ * HALO_NAT_NO_FLOW for a record that is not selected. Records and verdicts are read only; records
+ * 16-byte aligned, d_items / d_count / d_pos / d_workspace 4-byte aligned. One workspace serves
+ * any number of calls on one stream: the call re-initialises what it needs. HALO_E_RANGE, before
+ * any launch, when the slot count is not greater than n (or out of range as above); HALO_E_INVAL
+ * for a bad argument, a short workspace, or before the table's first sync; n == 0 is OK (*d_count
+ * = 0). Asynchronous on `stream`: one memset and five kernels. */
+HALO_API int halo_nat_collect_misses_device(const halo_nat_table_t* t, uint32_t dir,
+                                            const halo_rx_result_t* d_records, const uint8_t* d_verdict,
+                                            const uint8_t* d_select, uint32_t n, uint32_t scratch_log2,
+                                            halo_nat_miss_item_t* d_items, uint32_t cap, uint32_t* d_count,
+                                            uint32_t* d_pos, void* d_workspace, uint64_t workspace_bytes,
+                                            halo_stream_t stream);
+/* The same over compact records. */
+HALO_API int halo_nat_collect_misses_compact_device(const halo_nat_table_t* t, uint32_t dir,
+                                                    const halo_rx_record16_t* d_records, const uint8_t* d_verdict,
+                                                    const uint8_t* d_select, uint32_t n, uint32_t scratch_log2,
+                                                    halo_nat_miss_item_t* d_items, uint32_t cap, uint32_t* d_count,
+                                                    uint32_t* d_pos, void* d_workspace, uint64_t workspace_bytes,
+                                                    halo_stream_t stream);
+/* The same outputs from a sequential loop over host arrays: no device, no scratch. */
+HALO_API int halo_nat_collect_misses_host(const halo_nat_table_t* t, uint32_t dir, const halo_rx_result_t* records,
+                                          const uint8_t* verdict, const uint8_t* select, uint32_t n,
+                                          halo_nat_miss_item_t* items, uint32_t cap, uint32_t* count, uint32_t* pos);
+/* Resolve (host memory only): the loop body of halo_nat_resolve_misses over items[0..k) in order —
+ * the port mapping, then the host flow lookup, then NatAddFlow for LAN; nil becomes DROP, a WAN
+ * miss stays MISS (ip, port 0; ref HALO_NAT_NO_FLOW), a hit stamps the flow with `now`. answers[j]
+ * = {the translation, ref, verdict}; *n_added (optional) the flows added. */
+HALO_API int halo_nat_resolve_items(halo_nat_table_t* t, uint32_t dir, const halo_nat_miss_item_t* items, uint32_t k,
+                                    uint32_t now, halo_nat_answer_t* answers, uint32_t* n_added);
+/* Apply: for a record with d_pos[i] < k, by d_answers[d_pos[i]].verdict —
+ *   FLOW / MAPPING  what the device lookup would have written: ops[i].steps |= HALO_TX_NAT_DST (WAN)
+ *                   or _SRC (LAN) and this direction's ip and port, nothing else; d_verdict[i] and
+ *                   d_ref[i] are updated
+ *   DROP            d_verdict[i] = DROP, d_ref[i] = HALO_NAT_NO_FLOW; the op is left alone
+ *   MISS            nothing is written
+ * A record with d_pos[i] == HALO_NAT_NO_FLOW or d_pos[i] >= k (its representative was beyond the
+ * collect's cap) is left untouched: a later halo_nat_resolve_misses over what is still MISS
+ * finishes the batch in the right order. d_counts (optional; HALO_NAT_V_DROP + 1 u32) is
+ * INCREMENTED, per verdict, by the number of records with d_pos[i] < k. Ops and answers 16-byte
+ * aligned. Needs no table. Asynchronous on `stream`. */
+HALO_API int halo_nat_apply_answers_device(uint32_t dir, const uint32_t* d_pos, uint32_t n,
+                                           const halo_nat_answer_t* d_answers, uint32_t k, halo_tx_op_t* d_ops,
+                                           uint8_t* d_verdict, uint32_t* d_ref, uint32_t* d_counts,
+                                           halo_stream_t stream);
 
 /* ---- L2 switch: batched MAC learning and forwarding -----------------------------------------
  * engine.Switch / SwitchPort (engine/ethernet_engine.go:51-163, engine/engine.go:388-505): one MAC
